@@ -15,7 +15,19 @@ Workloads:
          `python bench.py --gpus N` with no torch.distributed environment launches
          the N rank processes itself (torch.distributed.run, before any GPU call).
 
-Fields beyond the driver contract:
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the result line; everything else below is measured only with --full.
+
+--dump-outputs DIR writes what the last timed step left in the product buffer (the array
+a caller of mpfft_mul_device receives) as float64 .npy files, each 64-bit limb as its
+(low, high) 32-bit halves so that every value is exact:
+  product_sample.npy      [K, 2]: the limbs at a fixed, seeded sample of K <= 2^20 positions
+                          (limbs 0 and n1 + n2 - 1 among them), in increasing position
+  product_chunk_sums.npy  [ceil((n1 + n2) / 4096), 2]: the sums of the low and of the high
+                          halves over every run of 4096 consecutive limbs (the whole product)
+The operands are seeded, so two builds run with the same arguments can be compared file by file.
+
+Fields beyond the driver contract (--full):
   roofline      the dominant kernel (largest stage time): algorithmic HBM bytes per
                 launch / its average duration from HIP events recorded inside the
                 timed region on the library's stream; traffic = FETCH+WRITE bytes per
@@ -332,6 +344,28 @@ def golden_digest(cfg):
         return None
 
 
+DUMP_SEED, DUMP_SAMPLE, DUMP_CHUNK = 0x5eed, 1 << 20, 4096
+
+
+def dump_outputs(path, prod):
+    """--dump-outputs: the product limbs `prod` (uint64, as the caller of the timed path receives
+    them) as float64 files of 32-bit halves (every value exact), about 17 MB at C3: a fixed seeded
+    sample of positions, and the per-chunk sums of the halves over the whole product (< 2^44)."""
+    os.makedirs(path, exist_ok=True)
+    prod = np.ascontiguousarray(prod, dtype=np.uint64)
+    n = prod.size
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(np.concatenate([rng.integers(0, n, size=min(n, DUMP_SAMPLE)), [0, n - 1]]))
+    s = prod[idx]
+    sample = np.stack([s & np.uint64(0xffffffff), s >> np.uint64(32)], axis=1).astype(np.float64)
+    pad = -n % DUMP_CHUNK
+    whole = np.concatenate([prod, np.zeros(pad, dtype=np.uint64)]) if pad else prod
+    halves = np.stack([whole & np.uint64(0xffffffff), whole >> np.uint64(32)], axis=1)
+    sums = halves.reshape(-1, DUMP_CHUNK, 2).sum(axis=1, dtype=np.uint64).astype(np.float64)
+    np.save(os.path.join(path, "product_sample.npy"), sample)
+    np.save(os.path.join(path, "product_chunk_sums.npy"), sums)
+
+
 def launch_ranks(args):
     """--gpus N without a torch.distributed environment: start N rank processes (no GPU
     has been touched in this process) and return their exit status."""
@@ -349,6 +383,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: beside the headline figure, also the stage breakdown and roofline, the exactness "
+                         "checks, the host-pointer (e2e) timing, the one-GPU C4 line and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write the product of the last timed step as DIR/<name>.npy (float64 halves of "
+                         "the limbs: a seeded sample and per-chunk sums; see the module docstring)")
     ap.add_argument("--config", default=None, choices=sorted(set(CONFIGS) | set(CONFIGS6)),
                     help="default: C3 at N = 1, C4 at N > 1 (M4: --mul6 only)")
     ap.add_argument("--mode", default=None, choices=["single", "replicas", "sharded", "multi"],
@@ -376,6 +416,9 @@ def main():
 
     if args.config and (args.config not in (CONFIGS6 if args.mul6 else CONFIGS)):
         ap.error(f"--config {args.config} is not a {'--mul6 ' if args.mul6 else ''}configuration")
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
+                              or args.mode not in (None, "single")):
+        ap.error("--dump-outputs writes the product of the single-GPU run (--gpus 1, the default mode)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
     if args.dry_run:
@@ -396,7 +439,7 @@ def main():
 
     # the multi-core CPU figure first: its worker processes start before anything touches the GPU
     ncore = None
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and not args.mul6 \
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_cpu_baseline and not args.mul6 \
             and args.mode in (None, "single") and args.cpu_procs > 0:
         ncore = cpu_ncore(args.config or "C3", args.cpu_procs)
 
@@ -518,6 +561,40 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
 
+    ms_step = el / args.steps * 1e3
+    value = world * (n1 + n2) * args.steps / el
+    res = {
+        "metric": METRIC,
+        "value": value,
+        "unit": "limbs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "scaling_note": "bench.py --gpus N > 1 splits one C4 product over the N GPUs (strong scaling); "
+                        "its N = 1 point is `c4_single` of a --full run (this line's value is C3, the largest "
+                        "single-GPU configuration)",
+        "vs_baseline": None,
+        "dtype": "u64",
+        "data": "synthetic (xoshiro256** limbs, seeds 0x1001/0x2002 per rank)",
+        "config": {"workload": f"{cfg}: new_mpn_mul depth={depth} w={w} n1=n2={nl} limbs "
+                               f"(l={P['l']} limbs/coeff, NC x NR = {P['NC']} x {P['NR']}, trunc={P['trunc']})",
+                   "parallelism": f"replicas x{world}" if world > 1 else "single"},
+    }
+
+    # the product of the last timed step, before anything else runs on the stream
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dr.cpu().numpy().view(np.uint64))
+
+    if not args.full:   # the plain run ends here: set-up, warm-up, the timed steps, the line
+        if rank == 0:
+            print(json.dumps(res))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # stage breakdown: K more multiplies in which the library records a HIP event on its own
     # stream at every stage boundary (mpfft_profile_begin) -- kept out of the timed loop above
     torch.cuda.synchronize(dev)
@@ -588,31 +665,11 @@ def main():
             dist.destroy_process_group()
         return
 
-    ms_step = el / args.steps * 1e3
-    value = world * (n1 + n2) * args.steps / el
     dname = max(stage_ms, key=stage_ms.get)
     roof = roofline(cfg, kern[dname], dname, stage_bytes(P, dname, n1, n2), stage_ms[dname])
     balg = b_alg(P, n1, n2)
     dev_ms = float(sum(stage_ms.values()))
-    res = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "limbs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "scaling_note": "bench.py --gpus N > 1 splits one C4 product over the N GPUs (strong scaling); "
-                        "its N = 1 point is `c4_single` below (this line's value is C3, the largest "
-                        "single-GPU configuration)",
-        "vs_baseline": None,
-        "dtype": "u64",
-        "data": "synthetic (xoshiro256** limbs, seeds 0x1001/0x2002 per rank)",
-        "config": {"workload": f"{cfg}: new_mpn_mul depth={depth} w={w} n1=n2={nl} limbs "
-                               f"(l={P['l']} limbs/coeff, NC x NR = {P['NC']} x {P['NR']}, trunc={P['trunc']})",
-                   "parallelism": f"replicas x{world}" if world > 1 else "single"},
+    res.update({
         "roofline": roof,
         "pipeline": {"device_ms": dev_ms, "b_alg_bytes": balg, "hbm_frac_b_alg": balg / (dev_ms * 1e-3) / HBM_PEAK,
                      "note": "whole multiply vs the HBM roofline of the three-pass MFA (SURVEY 8d)"},
@@ -622,7 +679,7 @@ def main():
         "e2e_host": e2e,
         "exact": exact,
         "exact_check": "SHA-256 of the product limbs vs tests/golden/products.json (GMP mpn_mul)",
-    }
+    })
     if world == 1 and not args.no_twin and cfg != "C4":
         del dr, ws
         torch.cuda.empty_cache()
@@ -661,6 +718,8 @@ def bench_mul6(args, mp, dev, cfg):
     torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
     got = dr.cpu().numpy().view(np.uint64)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, got)
     want = golden_digest(cfg) if cfg in CONFIGS and CONFIGS[cfg][2] == nl else None
     exact = hashlib.sha256(got.tobytes()).hexdigest() == want if want else None
     balg = b_alg(P, n1, n2)

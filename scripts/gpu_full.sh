@@ -1,12 +1,13 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd); export OUT=${OUT:-$ROOT/out}   # OUT: where this run's logs go
 # Whole GPU suite, then the C3 bench (with kernel stats) and the C4 bench, all digest-checked.
 # usage: scripts/gpu_full.sh <tag>
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out && T=${1:-x} && \
-timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread > gpurun_out/pytest_$T.log 2>&1 && \
-timeout -k 10 200 python3 -u bench.py --config C3 --steps 10 --no-cpu-baseline --e2e-reps 0 > gpurun_out/bench_c3_$T.log 2>&1 && \
-timeout -k 10 300 python3 -u bench.py --config C4 --steps 3 --warmup 1 --no-cpu-baseline --e2e-reps 0 > gpurun_out/bench_c4_$T.log 2>&1 && \
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/ks_$T -o c3 -- python3 bench.py --config C3 --steps 3 --warmup 1 --no-cpu-baseline --no-check --e2e-reps 0 > gpurun_out/ks_$T.log 2>&1
-rc=$?; echo "rc=$rc"; tail -3 gpurun_out/pytest_$T.log
-for c in c3 c4; do python3 -c "import json; d=json.loads(open('gpurun_out/bench_${c}_$T.log').read().strip().splitlines()[-1]); print('$c', round(d['ms_per_step'],3), d['exact'], {k: round(x,3) for k,x in d['stages_ms'].items()})" 2>/dev/null; done
-python3 scripts/kstats.py gpurun_out/ks_$T 2>/dev/null | head -24
+cd $ROOT && export TMPDIR=/tmp && mkdir -p $OUT && T=${1:-x} && \
+timeout -k 10 900 python3 -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread > $OUT/pytest_$T.log 2>&1 && \
+timeout -k 10 200 python3 -u bench.py --full --config C3 --steps 10 --no-cpu-baseline --e2e-reps 0 > $OUT/bench_c3_$T.log 2>&1 && \
+timeout -k 10 300 python3 -u bench.py --full --config C4 --steps 3 --warmup 1 --no-cpu-baseline --e2e-reps 0 > $OUT/bench_c4_$T.log 2>&1 && \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks_$T -o c3 -- python3 bench.py --full --config C3 --steps 3 --warmup 1 --no-cpu-baseline --no-check --e2e-reps 0 > $OUT/ks_$T.log 2>&1
+rc=$?; echo "rc=$rc"; tail -3 $OUT/pytest_$T.log
+for c in c3 c4; do python3 -c "import json; d=json.loads(open('$OUT/bench_${c}_$T.log').read().strip().splitlines()[-1]); print('$c', round(d['ms_per_step'],3), d['exact'], {k: round(x,3) for k,x in d['stages_ms'].items()})" 2>/dev/null; done
+python3 scripts/kstats.py $OUT/ks_$T 2>/dev/null | head -24
 exit $rc

@@ -1,12 +1,13 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd); export OUT=${OUT:-$ROOT/out}   # OUT: where this run's logs go
 # Round 6: forward k_rpass launches cover only the live groups (no early-exiting 1024-thread workgroups past the
 # truncation; every pass family from the second run on) against the previous library (libmpfft_prev.so): the whole GPU suite, C3 x2 / C4 / C2, rocprof at C3.
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out && L=$GRAFT_REPO_ROOT/mpir-fft_amd
+cd $ROOT && export TMPDIR=/tmp && mkdir -p $OUT && L=$ROOT/mpir-fft_amd
 rc=0
-timeout -k 10 900 python3 -u -m pytest tests -x -q --timeout 600 --timeout-method thread -m gpu > gpurun_out/lg2_pytest.log 2>&1 || rc=$?
+timeout -k 10 900 python3 -u -m pytest tests -x -q --timeout 600 --timeout-method thread -m gpu > $OUT/lg2_pytest.log 2>&1 || rc=$?
 run() {   # tag lib cfg steps
-  MPFFT_LIB=$2 timeout -k 10 300 python3 -u bench.py --config $3 --steps $4 --warmup 1 \
-    --no-cpu-baseline --e2e-reps 0 --no-twin > gpurun_out/lg2_$1.log 2>&1
+  MPFFT_LIB=$2 timeout -k 10 300 python3 -u bench.py --full --config $3 --steps $4 --warmup 1 \
+    --no-cpu-baseline --e2e-reps 0 --no-twin > $OUT/lg2_$1.log 2>&1
 }
 if [ $rc = 0 ]; then
   for rep in 1 2; do
@@ -16,17 +17,17 @@ if [ $rc = 0 ]; then
 fi
 [ $rc = 0 ] && { run c4_old $L/libmpfft_prev.so C4 3 && run c4_new $L/libmpfft.so C4 3 && run c2_old $L/libmpfft_prev.so C2 10 && run c2_new $L/libmpfft.so C2 10 || rc=$?; }
 [ $rc = 0 ] && { run c1_old $L/libmpfft_prev.so C1 20 && run c1_new $L/libmpfft.so C1 20 && run c0_old $L/libmpfft_prev.so C0 20 && run c0_new $L/libmpfft.so C0 20 || rc=$?; }
-[ $rc = 0 ] && { timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/lg2_prof -o c -- \
-    python3 bench.py --config C3 --steps 5 --warmup 1 --no-cpu-baseline --e2e-reps 0 --no-twin > gpurun_out/lg2_prof.log 2>&1 || rc=$?; }
+[ $rc = 0 ] && { timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lg2_prof -o c -- \
+    python3 bench.py --full --config C3 --steps 5 --warmup 1 --no-cpu-baseline --e2e-reps 0 --no-twin > $OUT/lg2_prof.log 2>&1 || rc=$?; }
 echo "rc=$rc"
-tail -n 2 gpurun_out/lg2_pytest.log
-for f in gpurun_out/lg2_c*.log; do python3 -c "
+tail -n 2 $OUT/lg2_pytest.log
+for f in $OUT/lg2_c*.log; do python3 -c "
 import json
 d=json.loads([l for l in open('$f') if l.startswith('{')][-1])
 print('$f', round(d['ms_per_step'],3), d['exact'], 'fwd_columns', round(d['stages_ms']['fwd_columns'],3))" 2>/dev/null || tail -n 3 $f; done
 [ $rc = 0 ] && python3 - <<'PY'
 import csv
-for r in csv.DictReader(open("gpurun_out/lg2_prof/c_kernel_stats.csv")):
+for r in csv.DictReader(open(__import__("os").environ["OUT"] + "/lg2_prof/c_kernel_stats.csv")):
     if "k_rpass<" in r["Name"] and ", 0, " in r["Name"]:
         print(r["Name"][:30], r["Calls"], round(float(r["AverageNs"])/1e3,1))
 PY

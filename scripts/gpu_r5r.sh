@@ -1,6 +1,7 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd); export OUT=${OUT:-$ROOT/out}   # OUT: where this run's logs go
 # Round 5, call R: per-pass phase stamps (diag build) of one C3 and one C4 multiply.
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out && T=${1:-r5r} && \
-MPFFT_LIB=diag MPFFT_RP_STAMPS=1 timeout -k 10 200 python3 -u bench.py --config C3 --steps 1 --warmup 0 --no-cpu-baseline --no-check --e2e-reps 0 --no-twin > gpurun_out/rp_stamps_c3_$T.log 2>&1 && \
-MPFFT_LIB=diag MPFFT_RP_STAMPS=1 timeout -k 10 200 python3 -u bench.py --config C4 --steps 1 --warmup 0 --no-cpu-baseline --no-check --e2e-reps 0 --no-twin > gpurun_out/rp_stamps_c4_$T.log 2>&1
-rc=$?; grep -h stamps gpurun_out/rp_stamps_c3_$T.log | sort | uniq -c | head -30; grep -h stamps gpurun_out/rp_stamps_c4_$T.log | sort | uniq -c | head -30; exit $rc
+cd $ROOT && export TMPDIR=/tmp && mkdir -p $OUT && T=${1:-r5r} && \
+MPFFT_LIB=diag MPFFT_RP_STAMPS=1 timeout -k 10 200 python3 -u bench.py --full --config C3 --steps 1 --warmup 0 --no-cpu-baseline --no-check --e2e-reps 0 --no-twin > $OUT/rp_stamps_c3_$T.log 2>&1 && \
+MPFFT_LIB=diag MPFFT_RP_STAMPS=1 timeout -k 10 200 python3 -u bench.py --full --config C4 --steps 1 --warmup 0 --no-cpu-baseline --no-check --e2e-reps 0 --no-twin > $OUT/rp_stamps_c4_$T.log 2>&1
+rc=$?; grep -h stamps $OUT/rp_stamps_c3_$T.log | sort | uniq -c | head -30; grep -h stamps $OUT/rp_stamps_c4_$T.log | sort | uniq -c | head -30; exit $rc

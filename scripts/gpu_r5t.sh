@@ -1,13 +1,14 @@
 #!/bin/bash
+ROOT=$(cd "$(dirname "$0")/.." && pwd); export OUT=${OUT:-$ROOT/out}   # OUT: where this run's logs go
 # Round 5, call T: k_pwss register pressure (parity suite, C3 / C4 benches)
 # parity suite, C3 / C4 benches.
-cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp && mkdir -p gpurun_out && T=${1:-r5t} && \
-timeout -k 10 600 python3 -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/pytest_$T.log 2>&1 && \
-tail -1 gpurun_out/pytest_$T.log && \
+cd $ROOT && export TMPDIR=/tmp && mkdir -p $OUT && T=${1:-r5t} && \
+timeout -k 10 600 python3 -u -m pytest tests/test_gpu_parity.py -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest_$T.log 2>&1 && \
+tail -1 $OUT/pytest_$T.log && \
 for r in 1 2; do
-  timeout -k 10 300 python3 -u bench.py --steps 20 --no-cpu-baseline --no-twin --e2e-reps 0 > gpurun_out/ab_${T}_c3_$r.log 2>&1 && \
-  timeout -k 10 300 python3 -u bench.py --config C4 --steps 3 --warmup 1 --no-cpu-baseline --e2e-reps 0 --no-twin > gpurun_out/ab_${T}_c4_$r.log 2>&1 || exit 1
+  timeout -k 10 300 python3 -u bench.py --full --steps 20 --no-cpu-baseline --no-twin --e2e-reps 0 > $OUT/ab_${T}_c3_$r.log 2>&1 && \
+  timeout -k 10 300 python3 -u bench.py --full --config C4 --steps 3 --warmup 1 --no-cpu-baseline --e2e-reps 0 --no-twin > $OUT/ab_${T}_c4_$r.log 2>&1 || exit 1
 done
 rc=$?; echo "rc=$rc"
-for f in gpurun_out/ab_${T}_*.log; do python3 -c "import json; d=json.loads([x for x in open('$f') if x.startswith('{')][-1]); s=d.get('stages_ms') or {}; print('$f', round(d['ms_per_step'],3), d.get('exact'), 'pw', round(s.get('pointwise'),3))" 2>/dev/null; done
+for f in $OUT/ab_${T}_*.log; do python3 -c "import json; d=json.loads([x for x in open('$f') if x.startswith('{')][-1]); s=d.get('stages_ms') or {}; print('$f', round(d['ms_per_step'],3), d.get('exact'), 'pw', round(s.get('pointwise'),3))" 2>/dev/null; done
 exit $rc
