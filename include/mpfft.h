@@ -277,6 +277,11 @@ int mpfft_last_ngpus(void);
 int mpfft_profile_begin(int max_calls);
 /* The kernel that carries each stage for these parameters, ';'-separated in MPFFT_STAGE_* order. */
 int mpfft_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len);
+/* The launches of the single-device truncated inverse column transform for these parameters, one
+ * per line, in order (a host-side dry run; no device needed): "k_rpass<levels,l/1024,dir,mode> pos
+ * off+len [fill lo= off=] [halfadd d1..d0]", "k_rpair<l/1024,op> off= h= i0= cnt=", "k_rchain<..>".
+ * MPFFT_EINVAL if buf is too small. */
+int mpfft_inv_columns_schedule(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len);
 int mpfft_profile_end(float *stage_ms, int *calls);
 
 const char *mpfft_strerror(int code);

@@ -345,6 +345,19 @@ def stage_kernels(n1, n2, depth, w):
     return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
 
 
+def inv_columns_schedule(n1, n2, depth, w):
+    """The launches of the single-device truncated inverse column transform, in order (a host-side
+    dry run: needs no GPU)."""
+    f = lib().mpfft_inv_columns_schedule
+    f.argtypes = [_L, _L, _UL, _UL, ctypes.c_char_p, ctypes.c_size_t]
+    f.restype = ctypes.c_int
+    buf = ctypes.create_string_buffer(1 << 16)
+    rc = f(n1, n2, depth, w, buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_inv_columns_schedule")
+    return buf.value.decode().splitlines()
+
+
 def profile_begin(max_calls):
     """Record HIP events at the stage boundaries of the next max_calls multiplies."""
     rc = lib().mpfft_profile_begin(max_calls)

@@ -65,6 +65,10 @@ struct PassArgs {
     // mode bit 2): positions p >= fill_lo also store 2^(p fill_rho) x_p at position p + fill_off
     int fill_lo, fill_off;
     u64 fill_rho;
+    // ... and the half-adds that follow it (itft1_r while t <= h) collapsed in that store: the
+    // distances fill_off/2, fill_off/4, .. down to fill_hmin (0: none) join the fill values of
+    // positions p and p + d for fill_lo <= p < d in registers, and only the surviving rows are stored
+    int fill_hmin;
     int grp0;            // k_rpass DIF: the first live group of a sub-array (the launch covers only the
                          // live groups, [grp0, grp0 + ngroups): no empty 1024-thread workgroups)
 };

@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "kernels.hpp"
@@ -435,7 +436,14 @@ struct Exec {
         static const int m = [] { const char *e = diag_env("MPFFT_CARRY_MASK"); return e ? atoi(e) : -1; }();
         return m >= 0 ? m : 5;
     }
-    struct Fill { long lo = 0, off = 0; u64 rho = 0; bool done = false; } fill;   // itft's FILL, see ifft_block
+    // itft's FILL, see ifft_block.  hmin: the smallest distance of the half-adds itft1_r runs next on the
+    // filled rows (0: none); habs: the pass took those of distance >= habs along (PassArgs::fill_hmin)
+    struct Fill { long lo = 0, off = 0; u64 rho = 0; bool done = false; long hmin = 0, habs = 0; } fill;
+    // single-GPU drivers: the half-adds after a FILL are offered to the pass that does the FILL
+    bool tail_fold = false;
+    // non-null: a dry run -- pass() and the pair steps append their launch to *rec and launch nothing
+    // (mpfft_inv_columns_schedule)
+    std::string *rec = nullptr;
     long dbl_lo = 0, dbl_hi = 0;
 
     Exec(const Plan &p, hipStream_t st) : P(p), s(st) { nw = P.tpb / 64; }
@@ -480,9 +488,28 @@ struct Exec {
     u32 *comb_flags(unsigned char *ws) const { return (u32 *)(ws + P.off_flags); }
     static long comb_flag_words(const Plan &P, long mcount) { return (comb_blocks(P, mcount) + 4) / 4 * 4; }
 
-    // single-GPU workspace: both layouts are the natural one
+    // what run_all sets for the whole single-GPU multiply (and the dry run of it)
+    void drive_single()
+    {
+        defer_double = true;   // itft + scale back to back
+        tail_fold = true;
+        fold = P.fold != 0;    // f4: no scaling pass, the combine reads the reduced form
+    }
+
+    // single-GPU workspace: both layouts are the natural one (ws null: a dry run, no views)
     void single(unsigned char *ws)
     {
+        c0 = 0;
+        ccount = (int)P.NC;
+        r0 = 0;
+        rcount = (int)P.Tr;
+        ccb = (int)P.NC;
+        cbb = P.lbC;
+        cbs = (long)P.Tr * P.NC;
+        if (!ws) {
+            col = row = cview = View{};
+            return;
+        }
         col.dig[0] = (u64 *)(ws + P.off_digA);
         col.top[0] = (int *)(ws + P.off_topA);
         col.cb[0] = (u64 *)(ws + P.off_cbA);
@@ -495,13 +522,6 @@ struct Exec {
             cview.top[0] = (int *)(ws + P.off_topC);
             cview.cb[0] = (u64 *)(ws + P.off_cbC);
         }
-        c0 = 0;
-        ccount = (int)P.NC;
-        r0 = 0;
-        rcount = (int)P.Tr;
-        ccb = (int)P.NC;
-        cbb = P.lbC;
-        cbs = (long)P.Tr * P.NC;
     }
 
     // both layouts start `slots` slots further on (the sqrt2 plan's second half)
@@ -591,6 +611,17 @@ struct Exec {
     int pass(PassArgs a, int logg, int dir, int nops)
     {
         const int rm = rp_mode(a, logg, dir);
+        if (rec) {
+            char ln[160];
+            int n = rm >= 0 ? snprintf(ln, sizeof ln, "k_rpass<%d,%d,%d,%d> pos %d+%d", logg, (int)P.l / 1024, dir, rm, a.pos_off, 1 << a.lbM)
+                            : snprintf(ln, sizeof ln, "pass<%d,%d> pos %d+%d", logg, dir, a.pos_off, 1 << a.lbM);
+            if (rm >= 0 && !rp_get((int)P.l, logg, dir, rm)) return MPFFT_EUNSUPPORTED;   // as the launch below
+            if (a.fill_off) n += snprintf(ln + n, sizeof ln - n, " fill lo=%d off=%d", a.fill_lo, a.fill_off);
+            if (a.fill_hmin) n += snprintf(ln + n, sizeof ln - n, " halfadd %d..%d", a.fill_off / 2, a.fill_hmin);
+            *rec += ln;
+            *rec += '\n';
+            return MPFFT_OK;
+        }
         if (rm >= 0) {
             rp_fn f = rp_get((int)P.l, logg, dir, rm);
             if (!f) return MPFFT_EUNSUPPORTED;
@@ -1035,9 +1066,15 @@ struct Exec {
                 f.fill_lo = (int)fill.lo;
                 f.fill_off = (int)fill.off;
                 f.fill_rho = fill.rho;
-                if (rp_mode(f, k, 1) >= 0) {
+                // the half-adds whose row pairs (p, p + d) sit in one group of this pass: d a multiple
+                // of its position step 2^(lbM - k) (d <= fill.off / 2 = 2^(k - 1) steps always is)
+                const long hm = std::max(fill.hmin, 1L << (lbM - k));
+                if (fill.hmin && hm <= fill.off / 2) f.fill_hmin = (int)hm;
+                const int fm = rp_mode(f, k, 1);
+                if (fm >= 0 && rp_get((int)P.l, k, 1, fm)) {
                     a = f;
                     fill.done = true;
+                    fill.habs = f.fill_hmin;
                 }
             }
             int rc = pass(a, k, 1, 1);
@@ -1104,6 +1141,12 @@ struct Exec {
             a.xoff = (int)off;
             rp_pair_fn f = rp_chain_get((int)P.l, chain.n);
             chain.n = 0;
+            if (rec) {
+                char ln[96];
+                snprintf(ln, sizeof ln, "k_rchain<%d,%d> off=%ld h=%ld cnt=%ld\n", (int)P.l / 1024, a.nb, off + h, h, cnt);
+                *rec += ln;
+                return MPFFT_OK;
+            }
             hipLaunchKernelGGL(f, dim3((unsigned)(cnt * ccount)), dim3(RP_NT), rp_chain_lds((int)P.l), s, a);
             HIPCHK(hipGetLastError());
             return MPFFT_OK;
@@ -1115,6 +1158,13 @@ struct Exec {
     int pairop_now(int op, long off, long h, long i0, long cnt, u64 rho)
     {
         if (cnt <= 0) return MPFFT_OK;
+        if (rec) {
+            char ln[96];
+            if (P.rpass) snprintf(ln, sizeof ln, "k_rpair<%d,%d> off=%ld h=%ld i0=%ld cnt=%ld\n", (int)P.l / 1024, op, off, h, i0, cnt);
+            else snprintf(ln, sizeof ln, "pair<%d> off=%ld h=%ld i0=%ld cnt=%ld\n", op, off, h, i0, cnt);
+            *rec += ln;
+            return MPFFT_OK;
+        }
         PairArgs a;
         a.dig = col.dig[0];
         a.cb = col.cb[0];
@@ -1189,13 +1239,18 @@ struct Exec {
             }
             return pairop(OP_DOUBLE, off, h, 0, t, 0);
         }
-        fill = {t - h, h, rho_blk(m), false};   // offered to ifft_block's last pass
+        // itft1_r(off + h, h, t - h) below half-adds at the distances h/2, h/4, .. while t - h is below them
+        long hmin = 0;
+        if (tail_fold)
+            for (long d = h / 2; d > t - h; d /= 2) hmin = d;
+        fill = {t - h, h, rho_blk(m), false, hmin, 0};   // offered to ifft_block's last pass
         rc = ifft_block(off, h);
         const bool filled = fill.done;
+        const long habs = fill.habs;
         fill = {};
         if (rc) return rc;
         if (!filled && (rc = pairop(OP_FILL, off, h, t - h, h - (t - h), rho_blk(m)))) return rc;
-        if ((rc = itft1_r(off + h, h, t - h))) return rc;
+        if ((rc = itft1_r(off + h, h, t - h, habs))) return rc;
         if ((rc = pairop(OP_IBFLY, off, h, 0, t - h, rho_blk(m)))) return rc;
         if (top) {
             dbl_lo = t - h;
@@ -1206,14 +1261,16 @@ struct Exec {
     }
 
     // IFFT_radix2_truncate1(_twiddle) (mul_fft.c:1604-1668): inputs [t, m) known
-    int itft1_r(long off, long m, long t)
+    // habs: the FILL pass before it has done the half-adds of distance >= habs (0: none); the
+    // blocks only shrink from here on, so those are the ones at the head of this recursion
+    int itft1_r(long off, long m, long t, long habs = 0)
     {
         int rc;
         const long h = m / 2;
         if (t == m) return ifft_block(off, m);
         if (t <= h) {
-            if ((rc = pairop(OP_HALFADD, off, h, t, h - t, 0))) return rc;
-            if ((rc = itft1_r(off, h, t))) return rc;
+            if (!(habs && h >= habs) && (rc = pairop(OP_HALFADD, off, h, t, h - t, 0))) return rc;
+            if ((rc = itft1_r(off, h, t, habs))) return rc;
             return pairop(OP_TWOXMY, off, h, 0, t, 0);
         }
         if ((rc = ifft_block(off, h))) return rc;
@@ -1524,8 +1581,7 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
     X.single(ws);
     X.zflags = X.comb_flags(ws);
     X.zflags_n = X.comb_flag_words(P, P.total);
-    X.defer_double = true;   // itft + scale back to back
-    X.fold = P.fold != 0;    // f4: no scaling pass, the combine reads the reduced form
+    X.drive_single();
     X.fuse_row_last = true;  // last row level inside the pointwise (nested negacyclic sizes)
     ProfCall pc;
     int rc;
@@ -1562,7 +1618,32 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
+// The launches of the truncated inverse column transform as run_all drives it, one per line: a dry
+// run of Exec::itft (Exec::rec), nothing touches the device.
+static std::string inv_columns_launches(const Plan &P)
+{
+    std::string out;
+    if (P.sqrt2) return out;
+    Exec X(P, nullptr);
+    X.single(nullptr);
+    X.drive_single();
+    X.rec = &out;
+    if (X.itft(0, P.NR, P.Tr)) out.clear();
+    return out;
+}
+
 extern "C" {
+
+int mpfft_inv_columns_schedule(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
+{
+    Plan P;
+    int rc = make_plan(&P, n1, n2, depth, w);
+    if (rc) return rc;
+    const std::string s = inv_columns_launches(P);
+    if (!buf || s.size() + 1 > len) return MPFFT_EINVAL;
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return MPFFT_OK;
+}
 
 // Which kernel carries each stage for these parameters (the same decisions Exec makes).
 int mpfft_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
@@ -1592,7 +1673,16 @@ int mpfft_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, 
                         : P.fold ? "(folded: 2^-(depth+1) in the last inverse row pass)"
                         : P.rpass ? "k_rscale" : P.wave ? "k_wscale" : "k_scale";
     const char *comb = P.fold ? "k_cmeta + k_combine_red (reduced form)" : "k_combine1";
-    snprintf(buf, len, "%s;%s;%s;%s;%s + %s;%s;%s", pass, rows, pw, pass, pass, pair, scale, comb);
+    // inverse columns: the FILL pass that also took the half-adds behind it is named with their distances
+    char invc[96];
+    int d1 = 0, d0 = 0;
+    const std::string sched = inv_columns_launches(P);
+    const size_t ha = sched.find(" halfadd ");
+    if (ha != std::string::npos && sscanf(sched.c_str() + ha, " halfadd %d..%d", &d1, &d0) == 2)
+        snprintf(invc, sizeof invc, "%s (FILL + half-add d=%d..%d) + %s", pass, d1, d0, pair);
+    else
+        snprintf(invc, sizeof invc, "%s + %s", pass, pair);
+    snprintf(buf, len, "%s;%s;%s;%s;%s;%s;%s", pass, rows, pw, pass, invc, scale, comb);
     return MPFFT_OK;
 }
 
@@ -1722,7 +1812,7 @@ int mpfft_stage(int stage, const uint64_t *d_i1, const uint64_t *d_i2, uint64_t 
     case MPFFT_STAGE_FWD_ROWS: return X.fwd_rows(2);
     case MPFFT_STAGE_POINTWISE: return X.pointwise();
     case MPFFT_STAGE_INV_ROWS: return X.inv_rows();
-    case MPFFT_STAGE_INV_COLUMNS: return X.itft(0, P.NR, P.Tr);
+    case MPFFT_STAGE_INV_COLUMNS: X.tail_fold = true; return X.itft(0, P.NR, P.Tr);
     case MPFFT_STAGE_SCALE: return X.scale();
     case MPFFT_STAGE_COMBINE: return X.combine_single(d_r, (unsigned char *)d_ws);
     case MPFFT_STAGE_FOLD_COMBINE: {

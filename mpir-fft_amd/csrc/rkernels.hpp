@@ -373,14 +373,16 @@ __device__ __forceinline__ u32 rp_pend(const PassArgs &a, const BGeo &g, int don
 }
 
 // x_i <- 2^E(i) x_i for all G slots (general exponents), NX slots per LDS round
-template <int G, int PP, int NX, int NT = RP_NT, typename EF>
+// (SK: a slot with E == 0 is not published either, as in rp_rot_all_al)
+template <int G, int PP, int NX, int NT = RP_NT, bool SK = false, typename EF>
 __device__ __forceinline__ void rp_rot_all(Pr (&x)[G][rp_r(PP, NT)], const RX<PP> &X, EF efn, u32 N, int t)
 {
     t = rp_launder(t);
 #pragma unroll
     for (int i0 = 0; i0 < G; i0 += NX) {
 #pragma unroll
-        for (int q = 0; q < NX && i0 + q < G; ++q) rp_pub<PP, NT>(X, q, x[i0 + q], t);
+        for (int q = 0; q < NX && i0 + q < G; ++q)
+            if (!SK || efn(i0 + q)) rp_pub<PP, NT>(X, q, x[i0 + q], t);
         __syncthreads();
 #pragma unroll
         for (int q = 0; q < NX && i0 + q < G; ++q) {
@@ -687,7 +689,8 @@ __device__ __forceinline__ void rp_pin(Pr (&x)[G][R])
 //               first level still runs in registers);
 //       DIR 1: bit 0 general final multipliers (inverse twiddle / scaling), bit 1 the pass
 //               holds the transform's last DIT level (h = 1: its first level needs no rotation),
-//               bit 2 the truncated inverse's FILL step (PassArgs::fill_*; not with bit 0),
+//               bit 2 the truncated inverse's FILL step (PassArgs::fill_*; not with bit 0), with
+//               fill_hmin also the half-adds that follow it, collapsed in that store,
 //               bit 3 the inverse MFA twiddle and the scaling applied on load (PassArgs::tw_mode
 //               3: the first pass of a column block, the rows' last pass then plain -- fold plans)
 // (compile-time, so the register-only level and the LDS level are never both in one kernel:
@@ -951,13 +954,62 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
         return DIR == 1 || (bs < a.need && bs + g.pstep > a.need_lo);
     }, (short *)smem, t);
     if (FILL) {   // IFFT_radix2_truncate's fill (mul_fft.c:1760-1764): b_(p+h) = 2^(p rho) a_p for p >= t - h
-        auto fills = [&](int s) -> bool { return g.pos0 + s * g.pstep >= a.fill_lo; };
+        // With fill_hmin the half-adds that IFFT_radix2_truncate1 (mul_fft.c:1604-1668) runs next on
+        // these rows are taken here too: at each distance d = fill_off/2, fill_off/4, .. >= fill_hmin
+        // the rows p + d, fill_lo <= p < d, are halved into row p and read by nothing afterwards.
+        // d is a multiple of the group's position step (host), so both rows are slots of this group:
+        // their fill values are summed in registers and the upper row is never written.  The
+        // halvings ride in the fill exponent: a value that takes part in c half-adds on its way is
+        // rotated by 2^(e - c) (at each distance both rows of a pair lie in [fill_lo, 2d), so both
+        // took part at every larger distance: all the terms of one sum share c).  The table goes
+        // over the exponent table, whose last readers (the levels) are barriers behind: EXPT[s] the
+        // exponent of slot s, EXPT[G + s] non-zero when its row is stored.
+        if (t < G) {
+            const int p = g.pos0 + t * g.pstep;
+            u32 e = 0, keep = 0;
+            if (p >= a.fill_lo) {
+                int q = p, c = 0;
+                for (int d = a.fill_off >> 1; a.fill_hmin && d >= a.fill_hmin; d >>= 1) {
+                    if (q >= a.fill_lo + d && q < 2 * d) {
+                        q -= d;
+                        ++c;
+                    } else if (q < d) {
+                        ++c;
+                    }
+                }
+                e = rp_mod2n((u32)(((u64)p * a.fill_rho) % N2) + N2 - (u32)c, N2);
+                keep = q == p;
+            }
+            EXPT[t] = e;
+            EXPT[G + t] = keep;
+        }
         __syncthreads();   // every HX read of the store done (the rotation reuses the exchange slots)
         if (t < G) SLT[t] += (u32)((long)a.fill_off * a.pos_stride);
-        rp_rot_all_al<G, PP, NX, NT>(x, X, [&](int s) -> u32 {
-            return fills(s) ? (u32)(((u64)(g.pos0 + s * g.pstep) * a.fill_rho) % N2) : 0u;
-        }, N, t);
-        rp_store<G, G, PP, NT>(x, st, SLT, fills, (short *)smem, t);
+        // register boundaries as after the levels (rp_pin), where they pay: the l = 4096 three-level
+        // kernels spill 80-96 B without them, the l = 2048 four-level ones 80-128 B with them
+        constexpr bool FPIN = PP == 4 && LOGG == 3;
+        if (FPIN) rp_pin<G, R>(x);
+        // one rotation routine for both cases: with no half-add taken every exponent is a whole number
+        // of limb pairs and rp_get_rot returns after its aligned read (a workgroup-uniform branch).  A
+        // runtime choice between this and rp_rot_all_al put 300-376 B of scratch into every kernel
+        // holding 16 limb pairs per thread; C2's plain FILL pass measures 153.5 -> 156.9 us with it
+        rp_rot_all<G, PP, NX, NT, true>(x, X, [&](int s) -> u32 { return rp_uniform(EXPT[s]); }, N, t);
+        if (FPIN) rp_pin<G, R>(x);
+        if (a.fill_hmin) {
+#pragma unroll
+            for (int dl = LOGG - 1; dl >= 0; --dl) {
+                const int ds = 1 << dl;
+                if (ds * g.pstep < a.fill_hmin) continue;   // workgroup-uniform, as the row bound below
+#pragma unroll
+                for (int s = 0; s < ds; ++s) {
+                    if (g.pos0 + s * g.pstep < a.fill_lo) continue;
+#pragma unroll
+                    for (int r = 0; r < R; ++r) x[s][r] = pr_add(x[s][r], x[s + ds][r]);
+                }
+            }
+            if (FPIN) rp_pin<G, R>(x);
+        }
+        rp_store<G, G, PP, NT>(x, st, SLT, [&](int s) -> bool { return rp_uniform(EXPT[G + s]) != 0; }, (short *)smem, t);
     }
     RP_STAMP(6);
     if (stamp) {
