@@ -275,7 +275,9 @@ int mpfft_last_ngpus(void);
  * the work); end synchronises and returns the summed per-stage milliseconds
  * (stage_ms[MPFFT_NSTAGES], MPFFT_STAGE_* order) and the number of profiled calls. */
 int mpfft_profile_begin(int max_calls);
-/* The kernel that carries each stage for these parameters, ';'-separated in MPFFT_STAGE_* order. */
+/* The kernel that carries each stage for these parameters, ';'-separated in MPFFT_STAGE_* order.
+ * Where k_rpass also splits the operands, the forward-column entry names that first pass's
+ * instance: "k_rpass (split: k_rpass<LOGG,PP,0,2>)". */
 int mpfft_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len);
 /* The launches of the single-device truncated inverse column transform for these parameters, one
  * per line, in order (a host-side dry run; no device needed): "k_rpass<levels,l/1024,dir,mode> pos

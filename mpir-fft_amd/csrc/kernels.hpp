@@ -40,7 +40,9 @@ struct PassArgs {
     long pbs;
     int sub_off;         // global index of sub-array 0 (row for the twiddle, column for the split)
     long jNC;            // fused split: coefficient index j = (pos_off + pos) * jNC + sub_off + sub
-    int zero_from;       // forward: positions >= zero_from are zero inputs
+    int zero_from;       // forward: positions >= zero_from are zero inputs (of every operand of the launch)
+    int zero_op[2];      // fused split (k_rpass MODE 2): the same bound per operand (grid row), rp_zero_row
+                         // of its own coefficient count where the host knows it, else zero_from
     int need;            // forward: only blocks starting below `need` are live
     int need_lo;         // forward: ... and ending above `need_lo` (a rank that needs only its own
                          // rows of the columns: replicated forward columns, mpfft_shard_stage 7)

@@ -801,7 +801,7 @@ struct Exec {
     PassArgs col_pass_args(int lvl) const
     {
         PassArgs a = col_args();
-        a.zero_from = (int)P.NR;
+        a.zero_from = a.zero_op[0] = a.zero_op[1] = (int)P.NR;
         a.lbM = P.lbR;
         a.lvl0 = lvl;
         a.rho = (u64)P.w * P.NC;
@@ -823,6 +823,16 @@ struct Exec {
                 a.src[1] = srcB; a.nsrc[1] = nB;
                 a.src_chunk = src_chunk;
                 a.zero_from = in_rows ? in_rows : (int)P.Tr;
+                a.zero_op[0] = a.zero_op[1] = a.zero_from;
+                if (srcA && srcB && !src_chunk && !in_rows) {
+                    // whole operands split by this pass: operand op ends in row ceil(j_op / NC) - 1, far
+                    // below the product's truncation row (C3: 78 of 156).  k_rpass takes its own
+                    // operand's bound by grid row; the other families take the larger of the two
+                    a.zero_op[0] = (int)rp_zero_row(P.j1, P.NC, P.Tr);
+                    a.zero_op[1] = (int)rp_zero_row(P.j2, P.NC, P.Tr);
+                    if (op >= 0) a.zero_op[0] = a.zero_op[1] = a.zero_op[op];   // only(a, op): grid row 0
+                    a.zero_from = std::max(a.zero_op[0], a.zero_op[1]);
+                }
                 a.zp = zflags;
                 a.zn = zflags_n;
             }
@@ -1632,6 +1642,20 @@ static std::string inv_columns_launches(const Plan &P)
     return out;
 }
 
+// The launches of the forward column transform on whole operands, one per line (a dry run as above)
+static std::string fwd_columns_launches(const Plan &P)
+{
+    std::string out;
+    if (P.sqrt2) return out;
+    static const u64 none = 0;   // a non-null operand pointer: the first pass splits (never read here)
+    Exec X(P, nullptr);
+    X.single(nullptr);
+    X.drive_single();
+    X.rec = &out;
+    if (X.fwd_columns(&none, P.n1, &none, P.n2, 2)) out.clear();
+    return out;
+}
+
 extern "C" {
 
 int mpfft_inv_columns_schedule(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
@@ -1682,7 +1706,14 @@ int mpfft_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, 
         snprintf(invc, sizeof invc, "%s (FILL + half-add d=%d..%d) + %s", pass, d1, d0, pair);
     else
         snprintf(invc, sizeof invc, "%s + %s", pass, pair);
-    snprintf(buf, len, "%s;%s;%s;%s;%s;%s;%s", pass, rows, pw, pass, invc, scale, comb);
+    // forward columns: where k_rpass also splits the operands, the first pass is named with its instance
+    char fwdc[64];
+    int fg = 0, fp = 0, fn = 0;
+    if (sscanf(fwd_columns_launches(P).c_str(), "k_rpass<%d,%d,0,2>%n", &fg, &fp, &fn) == 2 && fn > 0)
+        snprintf(fwdc, sizeof fwdc, "%s (split: k_rpass<%d,%d,0,2>)", pass, fg, fp);
+    else
+        snprintf(fwdc, sizeof fwdc, "%s", pass);
+    snprintf(buf, len, "%s;%s;%s;%s;%s;%s;%s", fwdc, rows, pw, pass, invc, scale, comb);
     return MPFFT_OK;
 }
 

@@ -43,6 +43,48 @@ inline int rp_maxlogg(int l) { return l == 1024 ? 3 : l == 2048 ? 3 : l == 4096 
 inline int rp_maxlogg_fwd4(int l) { return l == 2048 ? 4 : rp_maxlogg(l); }
 inline int rp_maxlogg_dit(int l) { return l == 2048 ? 4 : rp_maxlogg(l); }
 
+// ---- the split pass's zero bound (k_rpass MODE 2; host and device, tests/split_prune_host) ----
+#ifdef __HIPCC__
+#define RP_HD __host__ __device__
+#else
+#define RP_HD
+#endif
+// The first column row (position of the column transform) that holds no coefficient of an operand
+// of j coefficients: coefficient c lies in row c / NC, so a partly filled row is live.  Never past
+// `cap` (the rows the transform reads at all: the product's truncation row).
+RP_HD inline long rp_zero_row(long j, long NC, long cap)
+{
+    const long z = (j + NC - 1) / NC;
+    return z < cap ? z : cap;
+}
+// Live slots of a group holding positions pos0 + (i << lstep), i < G: those below the bound zf
+// (a prefix of the slots, the bound is monotone)
+RP_HD inline int rp_live_slots(int G, int pos0, int lstep, int zf)
+{
+    if (zf <= pos0) return 0;
+    const int n = (int)(((long)zf - pos0 + (1L << lstep) - 1) >> lstep);
+    return n < G ? n : G;
+}
+// the pair (= exchange slot) of DIF level li that partner slot k belongs to
+RP_HD inline int rp_pair_of(int logg, int li, int k)
+{
+    const int jb = logg - 1 - li;
+    return ((k >> (jb + 1)) << jb) | (k & ((1 << jb) - 1));
+}
+// Before DIF level li of a group of 2^logg slots whose first nlive inputs are live (the rest
+// zero), slot s holds a signed sum of the live inputs congruent to s mod 2^(logg - li).  Where
+// that class holds exactly one live input every butterfly on the way had a zero partner, so all
+// 2^li slots of the class are bit-for-bit copies of it.  For a partner slot k of level li (bit
+// logg - 1 - li set): is its class single, and which partner slot -- the lowest of the class --
+// represents it?  (rep = k itself when the class is not single.)
+RP_HD inline bool rp_class_single(int logg, int li, int nlive, int k, int &rep)
+{
+    const int m = 1 << (logg - li), c = k & (m - 1);
+    const bool single = c < nlive && c + m >= nlive;
+    rep = single ? c : k;
+    return single;
+}
+
 // LDS: NX exchange slots of 9 l bytes (limbs + 16-bit pair overflows) and the exponent
 // table.  <= 73 984 B, so two workgroups fit in 160 KiB (l = 4096, G = 8: 147 600 B, one).
 inline size_t rp_lds(int l, int logg)

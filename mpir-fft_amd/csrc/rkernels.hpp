@@ -271,8 +271,14 @@ __device__ __forceinline__ Pr rp_get_rot(const RX<PP> &X, int j, int pp, u32 e, 
 #ifndef RP_SPLIT_ZSKIP
 #define RP_SPLIT_ZSKIP 1   // 0 (A/B builds): the split pass exchanges its zero slots like any other
 #endif
+#ifndef RP_SPLIT_L0COPY
+#define RP_SPLIT_L0COPY 1  // 0 (A/B builds): the split pass's register level runs its butterflies on zero partners too
+#endif
+#ifndef RP_SPLIT_PUB1
+#define RP_SPLIT_PUB1 1    // 0 (A/B builds): the split pass publishes every live partner slot, copies included
+#endif
 #ifndef RP_SPLIT_LDS
-#define RP_SPLIT_LDS 1     // 0 (A/B builds): the split pass's per-slot guarded loads for whole operands too
+#define RP_SPLIT_LDS 1    // 0 (A/B builds): the split pass's per-slot guarded loads for whole operands too
 #endif
 #ifndef RP_SPLIT_PROBE
 #define RP_SPLIT_PROBE 0   // 1: timing probe, the split pass's source loads replaced by arithmetic (A/B builds only)
@@ -735,8 +741,11 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
         return g.sbase + (long)(ps >> a.pbb) * a.pbs + (long)(ps & ((1 << a.pbb) - 1)) * a.pos_stride;
     };
     auto slot_of = [&](int i) -> long { return wv_uniform(slot_lane(i)); };   // i wave-uniform: SGPRs
-    // zero inputs (positions >= zero_from) only occur in the split pass (host: rp_usable)
-    auto zero_in = [&](int i) -> bool { return SPLIT && g.pos0 + i * g.pstep >= a.zero_from; };
+    // zero inputs only occur in the split pass (host: rpass_mode): the positions at or past this
+    // operand's bound zero_op[op], so the group's first nlive slots are live and the rest zero
+    // (workgroup-uniform, one scalar compare per decision below)
+    const int nlive = SPLIT ? __builtin_amdgcn_readfirstlane(rp_live_slots(G, g.pos0, lobits, a.zero_op[op])) : G;
+    auto zero_in = [&](int i) -> bool { return SPLIT && i >= nlive; };
     // exponent table (rp_exp_entry) and the G slot indices: read back as uniform values
     // where needed (kept live from load to store, the 64-bit slot addresses spilled)
     constexpr int NEXP = 2 * G + (G / 2) * LOGG;
@@ -889,6 +898,16 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
             for (int pi = 0; pi < G / 2; ++pi) {
                 const int i = ((pi >> JB) << (JB + 1)) | (pi & ((1 << JB) - 1));
                 const int k = i | (1 << JB);
+                // split pass: a zero partner (workgroup-uniform) makes the butterfly a copy, bit for
+                // bit: x + 0 and x - 0 = x + ~0 + 1 both leave the five words of x as they are.  Not at
+                // l = 4096 with two levels (16 limb pairs per coefficient and thread): the branch put
+                // 24-28 B of scratch into that kernel, and all it saves is ten VALU operations a pair
+                constexpr bool L0COPY = RP_SPLIT_ZSKIP && RP_SPLIT_L0COPY && SPLIT && !(PP == 4 && LOGG == 2);
+                if (L0COPY && zero_in(k)) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) x[k][r] = x[i][r];
+                    continue;
+                }
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
                     const Pr y = x[k][r];
@@ -899,18 +918,28 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
             continue;
         }
         // partner x_k read rotated by E: (x_i, x_k) <- (x_i + 2^E x_k, x_i - 2^E x_k)
-        // Split pass: the input slots at or past zero_from are zero (zero_in is monotone in the
-        // slot), so before DIF level li >= 1 slot s is zero iff input slot s mod 2^(LOGG - li)
+        // Split pass: the input slots at or past the operand's bound are zero (zero_in is monotone
+        // in the slot), so before DIF level li >= 1 slot s is zero iff input slot s mod 2^(LOGG - li)
         // was.  A zero partner is neither published nor read: (x_i, x_k) <- (x_i, x_i), bit for
-        // bit what the butterfly gives (workgroup-uniform; C3's pass-0 groups hold 4-5 live
-        // slots of 16, so level 1 exchanges 0-2 of its 8 pairs)
+        // bit what the butterfly gives (workgroup-uniform).  The bound is the operand's own last row
+        // (PassArgs::zero_op, not the product's truncation row): C3's pass-0 groups hold 4-5 live
+        // slots of 16, so level 1 exchanges 0-2 of its 8 pairs.
+        // Where the partner's class mod 2^(LOGG - li) holds one live input, its 2^li slots are copies
+        // of each other (rp_class_single; the pending exponents differ, but they live in EXPT, not in
+        // the registers): only the lowest is published, and every pair of the class reads that one
+        // exchange slot with its own exponent.  xs(pi): the exchange slot pair pi reads (uniform).
         auto pz = [&](int k) -> bool { return RP_SPLIT_ZSKIP && SPLIT && zero_in(k & ((1 << (LOGG - li)) - 1)); };
+        auto xs = [&](int pi, int k) -> int {
+            int rep = k;
+            if (RP_SPLIT_ZSKIP && RP_SPLIT_PUB1 && SPLIT && rp_class_single(LOGG, li, nlive, k, rep)) return rp_pair_of(LOGG, li, rep);
+            return pi;
+        };
         const int tl = rp_launder(t);
         bool xch = false;
 #pragma unroll
         for (int pi = 0; pi < G / 2; ++pi) {
             const int i = ((pi >> JB) << (JB + 1)) | (pi & ((1 << JB) - 1));
-            if (pz(i | (1 << JB))) continue;
+            if (pz(i | (1 << JB)) || xs(pi, i | (1 << JB)) != pi) continue;
             rp_pub<PP, NT>(X, pi, x[i | (1 << JB)], tl);
             xch = true;
         }
@@ -925,11 +954,12 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
                 continue;
             }
             const u32 E = rp_uniform(EXPT[2 * G + (G / 2) * li + pi]);
+            const int xp = xs(pi, k);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 if (r % 2 == 0) RP_FENCE();   // two partner reads in flight at a time
                 bool ng;
-                const Pr y = rp_get_al<PP>(X, pi, tl + NT * r, E, N, ng);
+                const Pr y = rp_get_al<PP>(X, xp, tl + NT * r, E, N, ng);
                 pr_bfly(x[i][r], x[k][r], x[i][r], y, ng);
             }
         }
