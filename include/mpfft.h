@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 2
+#define MPFFT_VERSION 3
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -79,6 +79,31 @@ int mpfft_check_params(long n1, long n2, unsigned long depth, unsigned long w);
 /* out[10] = n, l, NC (= sqrt, columns), j1, j2, trunc, bits1, NR (rows), threads/workgroup, limbs/thread
  * (mul_fft.c:3193-3203). */
 int mpfft_plan_info(long n1, long n2, unsigned long depth, unsigned long w, long *out);
+
+/* ---- squaring (MPFFT_VERSION 3): r[0 .. 2n) = a[0 .. n)^2, exact, with new_mpn_mul's meaning of
+ * (depth, w).  One operand is split and transformed once, the workspace holds no second
+ * coefficient array, and the nested pointwise runs its squaring kernel (k_pwsq: one inner forward
+ * transform, about half the digit products).  new_mpn_mul / mpfft_mul_ex given the same pointer
+ * twice still run the multiply.  Parameter validation and status codes are those of
+ * mpfft_check_params(n, n, depth, w); r may not overlap a.
+ * Not covered: the sqrt2 front end (new_mpn_mul6), the sharded / multi-GPU entries and
+ * mpfft_set_devices routing -- a square always runs on the calling thread's device. */
+int mpfft_sqr_ex(uint64_t *r, const uint64_t *a, long n, unsigned long depth, unsigned long w);
+/* mpn_sqr-style entry: (depth, w) = mpfft_choose(n, n) (host pointers). */
+int mpfft_sqr_auto(uint64_t *r, const uint64_t *a, long n);
+/* Device-resident square, queued on `stream`; d_ws holds mpfft_sqr_workspace_bytes(n, depth, w). */
+int mpfft_sqr_device(uint64_t *d_r, const uint64_t *d_a, long n, unsigned long depth, unsigned long w,
+                     void *d_ws, size_t ws_bytes, void *stream);
+/* mpfft_workspace_bytes(n, n, depth, w) less operand B's limb, top and carry-mask arrays. */
+size_t mpfft_sqr_workspace_bytes(long n, unsigned long depth, unsigned long w);
+/* out[8] as mpfft_workspace_layout, entries 3..5 (the B arrays) 0. */
+int mpfft_sqr_workspace_layout(long n, unsigned long depth, unsigned long w, size_t *out);
+/* One MPFFT_STAGE_* stage on the square's workspace, operand 0 only. */
+int mpfft_sqr_stage(int stage, const uint64_t *d_a, uint64_t *d_r, long n, unsigned long depth,
+                    unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* As mpfft_stage_kernels(n, n, ...), the pointwise field "k_pwsq<M>..." on nested plans and
+ * "<kernel> (B = A)" where a multiply kernel runs with A's arrays as both operands. */
+int mpfft_sqr_stage_kernels(long n, unsigned long depth, unsigned long w, char *buf, size_t len);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity
@@ -270,7 +295,7 @@ int mpfft_set_devices(int ngpus, const int *devices, long min_l);
 int mpfft_last_ngpus(void);
 
 /* Stage profiling of the whole-multiply entries (new_mpn_mul, mpfft_mul_ex,
- * mpfft_mul_device): between begin and end, each of the next max_calls multiplies
+ * mpfft_mul_device, and the squares mpfft_sqr_ex / mpfft_sqr_device): between begin and end, each of the next max_calls multiplies
  * records a HIP event on its own stream at every stage boundary (no other change to
  * the work); end synchronises and returns the summed per-stage milliseconds
  * (stage_ms[MPFFT_NSTAGES], MPFFT_STAGE_* order) and the number of profiled calls. */

@@ -166,6 +166,21 @@ def lib():
         h.mpfft_check_params6.restype = ctypes.c_int
         h.mpfft_plan_info6.argtypes = [_L, _L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
         h.mpfft_plan_info6.restype = ctypes.c_int
+        if hasattr(h, "mpfft_sqr_ex"):   # MPFFT_VERSION 3 (older libraries in A/B runs lack them)
+            h.mpfft_sqr_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_sqr_ex.restype = ctypes.c_int
+            h.mpfft_sqr_auto.argtypes = [_u64p, _u64p, _L]
+            h.mpfft_sqr_auto.restype = ctypes.c_int
+            h.mpfft_sqr_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
+            h.mpfft_sqr_device.restype = ctypes.c_int
+            h.mpfft_sqr_workspace_bytes.argtypes = [_L, _UL, _UL]
+            h.mpfft_sqr_workspace_bytes.restype = ctypes.c_size_t
+            h.mpfft_sqr_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_size_t)]
+            h.mpfft_sqr_workspace_layout.restype = ctypes.c_int
+            h.mpfft_sqr_stage.argtypes = [ctypes.c_int, _vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
+            h.mpfft_sqr_stage.restype = ctypes.c_int
+            h.mpfft_sqr_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_char_p, ctypes.c_size_t]
+            h.mpfft_sqr_stage_kernels.restype = ctypes.c_int
         _lib = h
     return _lib
 
@@ -399,6 +414,86 @@ def workspace_views(ws, n1, n2, depth, w):
     def top(off):
         return u8[off:off + slots * 4].view(torch.int32)
     return dig(lay["digA"]), top(lay["topA"]), dig(lay["digB"]), top(lay["topB"])
+
+
+# ---- squaring (mpfft_sqr_*, include/mpfft.h): one operand, no B arrays in the workspace ----
+
+def sqr(a, depth, w):
+    """The 2n-limb square of `a` as a new uint64 array (host pointers, mpfft_sqr_ex)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    r = np.zeros(2 * len(a), dtype=np.uint64)
+    rc = lib().mpfft_sqr_ex(_p(r), _p(a), len(a), depth, w)
+    if rc:
+        raise MpfftError(rc, f"sqr(n={len(a)}, depth={depth}, w={w})")
+    return r
+
+
+def sqr_auto(a):
+    """mpn_sqr-style square with (depth, w) from choose(n, n)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    r = np.zeros(2 * len(a), dtype=np.uint64)
+    rc = lib().mpfft_sqr_auto(_p(r), _p(a), len(a))
+    if rc:
+        raise MpfftError(rc, f"sqr_auto(n={len(a)})")
+    return r
+
+
+def sqr_workspace_bytes(n, depth, w):
+    return int(lib().mpfft_sqr_workspace_bytes(n, depth, w))
+
+
+def alloc_workspace_sqr(n, depth, w, device="cuda"):
+    import torch
+    nb = sqr_workspace_bytes(n, depth, w)
+    if nb == 0:
+        raise MpfftError(check_params(n, n, depth, w), "sqr workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def sqr_device(d_r, d_a, n, depth, w, ws, stream=None):
+    """d_r[:2n] = d_a[:n]^2, all tensors on the GPU; queued on `stream`, not synchronised."""
+    rc = lib().mpfft_sqr_device(_ptr(d_r), _ptr(d_a), n, depth, w, _ptr(ws),
+                                ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_sqr_device")
+
+
+def sqr_stage(which, d_a, d_r, n, depth, w, ws, stream=None):
+    rc = lib().mpfft_sqr_stage(which, _ptr(d_a), _ptr(d_r), n, depth, w, _ptr(ws),
+                               ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_sqr_stage({which})")
+
+
+def sqr_stage_kernels(n, depth, w):
+    """dict stage -> the kernel a square launches for it (the pointwise: k_pwsq<M>... or
+    '<kernel> (B = A)')"""
+    buf = ctypes.create_string_buffer(512)
+    rc = lib().mpfft_sqr_stage_kernels(n, depth, w, buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_sqr_stage_kernels")
+    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+
+
+def sqr_workspace_layout(n, depth, w):
+    out = (ctypes.c_size_t * 8)()
+    rc = lib().mpfft_sqr_workspace_layout(n, depth, w, out)
+    if rc:
+        raise MpfftError(rc, "sqr_workspace_layout")
+    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
+    return dict(zip(keys, list(out)))
+
+
+def sqr_workspace_views(ws, n, depth, w):
+    """(digA, topA) views into a square's workspace tensor (slot-major), as workspace_views."""
+    import torch
+    P = plan_info(n, n, depth, w)
+    lay = sqr_workspace_layout(n, depth, w)
+    slots, l = lay["slots"], P["l"]
+    u8 = ws.view(torch.uint8)
+    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
+    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
+    return dig, top
 
 
 # ---- sharded (multi-GPU) stages: see sharded.py ------------------------------

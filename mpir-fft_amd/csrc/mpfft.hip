@@ -99,6 +99,7 @@ struct Plan {
     size_t off_meta;    // k_cmeta's per-coefficient A_k, B_k (fold plans)
     int fuse_rows;      // row DIF levels that run inside the pointwise: 1 (slot pairs), 2 (slot quads), 0
     size_t off_digC, off_topC, off_cbC;
+    bool sqr;           // squaring plan (make_plan_sqr): one operand, no B arrays in the layout
 };
 
 static int ilog2(long v) { int d = 0; while ((1L << d) < v) ++d; return d; }
@@ -338,6 +339,27 @@ static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned lo
     return MPFFT_OK;
 }
 
+// Squaring plan: the multiply's plan for n by n limbs -- the same split, trunc, fold, ltw and
+// fuse_rows -- with operand B's arrays (dig + top + cbb of make_plan_split) taken out of the
+// layout: everything behind them moves down by their size.
+static int make_plan_sqr(Plan *p, long n, unsigned long depth, unsigned long w)
+{
+    const int rc = make_plan(p, n, n, depth, w);
+    if (rc) return rc;
+    const size_t b = (p->has_c ? p->off_digC : p->off_flags) - p->off_digB;
+    p->sqr = true;
+    p->off_digB = p->off_topB = p->off_cbB = 0;
+    if (p->has_c) {
+        p->off_digC -= b;
+        p->off_topC -= b;
+        p->off_cbC -= b;
+    }
+    p->off_flags -= b;
+    p->off_meta -= b;
+    p->bytes -= b;
+    return MPFFT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // kernel dispatch
 // ---------------------------------------------------------------------------
@@ -516,6 +538,11 @@ struct Exec {
         col.dig[1] = (u64 *)(ws + P.off_digB);
         col.top[1] = (int *)(ws + P.off_topB);
         col.cb[1] = (u64 *)(ws + P.off_cbB);
+        if (P.sqr) {   // no B arrays: operand 1 is operand 0 (the passes run operand 0 only)
+            col.dig[1] = col.dig[0];
+            col.top[1] = col.top[0];
+            col.cb[1] = col.cb[0];
+        }
         row = col;
         if (P.has_c) {
             cview.dig[0] = (u64 *)(ws + P.off_digC);
@@ -928,18 +955,24 @@ struct Exec {
             const int fz = row_fused();
             const bool pair = fz > 0;
             pw_fn f = pw_get(M, lk, fz);
+            pw_sq_fn fs = P.sqr ? pw_get_sqr(M, lk, fz) : nullptr;
+            if (P.sqr && f && !fs) return MPFFT_EUNSUPPORTED;   // a missing squaring instance is an error
             if (f) {
                 const size_t lds = pw_lds(M, 1 << lk, (int)P.l);
-                allow_lds((const void *)f, lds);
+                allow_lds(fs ? (const void *)fs : (const void *)f, lds);
                 static const bool stamps = diag_env("MPFFT_PW_STAMPS") != nullptr;
                 unsigned long long *dbg = nullptr;
                 if (stamps) {   // diagnostics only: per-workgroup phase stamps, averaged on the host
                     HIPCHK(hipMalloc((void **)&dbg, (size_t)cnt * 64));
                     HIPCHK(hipMemsetAsync(dbg, 0, (size_t)cnt * 64, s));
                 }
-                hipLaunchKernelGGL(f, dim3((unsigned)cnt), dim3(1u << lk), lds, s, row.dig[0], row.cb[0], row.top[0],
-                                   (const u64 *)row.dig[1], (const u64 *)row.cb[1], (const int *)row.top[1], (int)P.l,
-                                   cview.dig[0], cview.cb[0], cview.top[0], dbg);
+                if (fs)   // squaring plan: k_pwsq, the same grid, block and LDS
+                    hipLaunchKernelGGL(fs, dim3((unsigned)cnt), dim3(1u << lk), lds, s, row.dig[0], row.cb[0], row.top[0],
+                                       (int)P.l, cview.dig[0], cview.cb[0], cview.top[0], dbg);
+                else
+                    hipLaunchKernelGGL(f, dim3((unsigned)cnt), dim3(1u << lk), lds, s, row.dig[0], row.cb[0], row.top[0],
+                                       (const u64 *)row.dig[1], (const u64 *)row.cb[1], (const int *)row.top[1], (int)P.l,
+                                       cview.dig[0], cview.cb[0], cview.top[0], dbg);
                 HIPCHK(hipGetLastError());
                 if (pair) {   // the product lives in C from here on (single layout: rows == columns)
                     row.dig[0] = col.dig[0] = cview.dig[0];
@@ -966,6 +999,12 @@ struct Exec {
                 return MPFFT_OK;
             }
         }
+        // Squaring plans reach the four families below with A's arrays as B as well (Exec::single).
+        // That is safe in place: in each of k_pwm2, k_pwm, k_pw and k_pointwise a thread reads
+        // topB[slot] and its limbs of B at the very point where it reads topA[slot] and the same
+        // limbs of A (into registers or LDS), and A is only written by normalize_store at the
+        // end -- B == A adds no read that the multiply does not already order before that write
+        // (nothing is __restrict__).
         static const long pwm2_maxl = [] { const char *e = diag_env("MPFFT_PWM2_MAXL"); return e ? atol(e) : 4096L; }();
         if (P.l % 256 == 0 && P.l <= pwm2_maxl && pw_kind() != PW_MFMA1 && pw_kind() != PW_VALU) {   // int8 MFMA, register-blocked: 2 fold tiles per wave
             const int nw = (int)P.l / 256;
@@ -1625,6 +1664,40 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
     return rc;
 }
 
+// The square of one operand (make_plan_sqr): run_all with operand 0 alone -- one split, one
+// forward column and row transform (nops = 1; that pass still clears the combine flags), the
+// pointwise in squaring mode (k_pwsq, or the other families with B = A), then the multiply's
+// inverse, scaling and combine unchanged.
+// Out of scope here: the sqrt2 front end (new_mpn_mul6), the sharded and multi-GPU entries and
+// mpfft_set_devices routing -- a square always runs on the calling thread's device.
+static int run_sqr(const Plan &P, u64 *d_r, const u64 *d_a, unsigned char *ws, hipStream_t s)
+{
+    Exec X(P, s);
+    X.single(ws);
+    X.zflags = X.comb_flags(ws);
+    X.zflags_n = X.comb_flag_words(P, P.total);
+    X.drive_single();
+    X.fuse_row_last = true;
+    ProfCall pc;
+    int rc;
+    pc.mark(0, s);
+    if ((rc = X.fwd_columns(d_a, P.n1, d_a, P.n1, 1, 0))) return rc;
+    pc.mark(1, s);
+    if ((rc = X.fwd_rows(1, 0))) return rc;
+    pc.mark(2, s);
+    if ((rc = X.pointwise())) return rc;
+    pc.mark(3, s);
+    if ((rc = X.inv_rows())) return rc;
+    pc.mark(4, s);
+    if ((rc = X.itft(0, P.NR, P.Tr))) return rc;
+    pc.mark(5, s);
+    if ((rc = X.scale())) return rc;
+    pc.mark(6, s);
+    rc = X.fold ? X.combine_fold(d_r, ws, X.dbl_lo, X.dbl_hi) : X.combine_single(d_r, ws);
+    pc.mark(7, s);
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -2165,6 +2238,118 @@ void new_mpn_mul6(mp_limb_t *r1, mp_limb_t *i1, mp_size_t n1, mp_limb_t *i2, mp_
     }
 }
 
+// ---- squaring entries (run_sqr) ---------------------------------------------------------
+size_t mpfft_sqr_workspace_bytes(long n, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan_sqr(&P, n, depth, w)) return 0;
+    return P.bytes;
+}
+
+int mpfft_sqr_workspace_layout(long n, unsigned long depth, unsigned long w, size_t *out)
+{
+    Plan P;
+    int rc = make_plan_sqr(&P, n, depth, w);
+    if (rc) return rc;
+    out[0] = P.off_digA; out[1] = P.off_topA; out[2] = P.off_cbA;
+    out[3] = out[4] = out[5] = 0;   // no B arrays
+    out[6] = P.slots; out[7] = (size_t)cb_words((int)P.l);
+    return MPFFT_OK;
+}
+
+int mpfft_sqr_device(uint64_t *d_r, const uint64_t *d_a, long n, unsigned long depth, unsigned long w,
+                     void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_sqr(&P, n, depth, w);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    return run_sqr(P, d_r, d_a, (unsigned char *)d_ws, (hipStream_t)stream);
+}
+
+int mpfft_sqr_stage(int stage, const uint64_t *d_a, uint64_t *d_r, long n, unsigned long depth,
+                    unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_sqr(&P, n, depth, w);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    Exec X(P, (hipStream_t)stream);
+    X.single((unsigned char *)d_ws);
+    switch (stage) {
+    case MPFFT_STAGE_FWD_COLUMNS: return X.fwd_columns(d_a, n, d_a, n, 1, 0);
+    case MPFFT_STAGE_FWD_ROWS: return X.fwd_rows(1, 0);
+    case MPFFT_STAGE_POINTWISE: return X.pointwise();
+    case MPFFT_STAGE_INV_ROWS: return X.inv_rows();
+    case MPFFT_STAGE_INV_COLUMNS: X.tail_fold = true; return X.itft(0, P.NR, P.Tr);
+    case MPFFT_STAGE_SCALE: return X.scale();
+    case MPFFT_STAGE_COMBINE: return X.combine_single(d_r, (unsigned char *)d_ws);
+    case MPFFT_STAGE_FOLD_COMBINE: {
+        if (!P.fold) return MPFFT_EUNSUPPORTED;
+        long lo, hi;
+        plan_dbl(P, &lo, &hi);
+        return X.combine_fold(d_r, (unsigned char *)d_ws, lo, hi);
+    }
+    }
+    return MPFFT_EINVAL;
+}
+
+// the multiply's fields for (n, n) with the pointwise renamed: k_pwsq<M>... on nested plans,
+// "<kernel> (B = A)" on the others
+int mpfft_sqr_stage_kernels(long n, unsigned long depth, unsigned long w, char *buf, size_t len)
+{
+    char mul[512];
+    int rc = mpfft_stage_kernels(n, n, depth, w, mul, sizeof mul);
+    if (rc) return rc;
+    std::string out;
+    int field = 0;
+    const char *p = mul;
+    while (true) {
+        const char *e = strchr(p, ';');
+        std::string f = e ? std::string(p, e) : std::string(p);
+        if (field == 2) {
+            if (!f.compare(0, 7, "k_pwss<")) f.replace(0, 6, "k_pwsq");
+            else f += " (B = A)";
+        }
+        if (field) out += ';';
+        out += f;
+        ++field;
+        if (!e) break;
+        p = e + 1;
+    }
+    if (!buf || out.size() + 1 > len) return MPFFT_EINVAL;
+    memcpy(buf, out.c_str(), out.size() + 1);
+    return MPFFT_OK;
+}
+
+// host-pointer square: one H2D copy of n limbs on the context's stream (no copy stream, no event
+// wait), io = operand + 2n result limbs; the same per-device context, lock and grow-only buffers
+// as mul_host
+int mpfft_sqr_ex(uint64_t *r, const uint64_t *a, long n, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_sqr(&P, n, depth, w);
+    if (rc) return rc;
+    (void)hipGetLastError();
+    int ndev = 0, dev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
+    DevCtx &C = g_dev[dev];
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
+    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, (size_t)3 * n * 8))) return rc;
+    u64 *d_a = C.io, *d_r = C.io + n;
+    HIPCHK(hipMemcpyAsync(d_a, a, (size_t)n * 8, hipMemcpyHostToDevice, C.stream));
+    if ((rc = run_sqr(P, d_r, d_a, C.ws, C.stream))) return rc;
+    HIPCHK(hipMemcpyAsync(r, d_r, (size_t)2 * n * 8, hipMemcpyDeviceToHost, C.stream));
+    HIPCHK(hipStreamSynchronize(C.stream));
+    g_last_ngpus = 1;
+    return MPFFT_OK;
+}
+
 // release the calling device's cached workspace (the next call re-allocates)
 int mpfft_release(void)
 {
@@ -2231,6 +2416,14 @@ int mpfft_mul_auto(uint64_t *r1, const uint64_t *i1, long n1, const uint64_t *i2
     const int rc = mpfft_choose(n1, n2, &d, &wv);
     if (rc) return rc;
     return mpfft_mul_ex(r1, i1, n1, i2, n2, d, wv);
+}
+
+int mpfft_sqr_auto(uint64_t *r, const uint64_t *a, long n)
+{
+    unsigned long d = 0, wv = 0;
+    const int rc = mpfft_choose(n, n, &d, &wv);
+    if (rc) return rc;
+    return mpfft_sqr_ex(r, a, n, d, wv);
 }
 
 // mul_fft.c:3190 -- same signature and meaning; fails loudly instead of segfaulting

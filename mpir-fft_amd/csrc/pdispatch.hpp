@@ -13,6 +13,11 @@ typedef void (*pw_fn)(uint64_t *, uint64_t *, int *, const uint64_t *, const uin
 pw_fn pw_get(int M, int lk, int fuse = 0);
 size_t pw_lds(int M, int K, int l);
 
+// k_pwsq<M, lk, fuse>: the squaring form (A <- A^2, no operand B), the same instances, LDS and
+// launch shape as k_pwss; nullptr if not built
+typedef void (*pw_sq_fn)(uint64_t *, uint64_t *, int *, int, uint64_t *, uint64_t *, int *, unsigned long long *);
+pw_sq_fn pw_get_sqr(int M, int lk, int fuse = 0);
+
 // Inner ring for a product mod 2^(64 l) + 1 cut into K = 2^lk pieces: the smallest even M
 // (limbs) with 64 M >= 2 (64 l / K) + lk + 4: the pair-fused inputs (pieces of x0 +- x1) are
 // below 2^(B+1) (1 + 2^-64) in magnitude, so |c_t| < K 2^(2B+2) (1 + 2^-62) < 2^(N'-1)

@@ -1191,3 +1191,206 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();
     }
 }
+
+// ---------------------------------------------------------------------------
+// squaring: A[slot] <- A[slot]^2 (k_pwsq).  One operand, so one set of pieces, one forward
+// transform and a digit product that forms every off-diagonal term once.
+// ---------------------------------------------------------------------------
+
+// z = a^2 mod p' for canonical a (La, ta); result limbs + top (value = L + T 2^N').
+// One digit array: column c sums the products ad[i] ad[c - i], i < c - i, once and doubles the
+// sum, plus ad[c/2]^2 for even c -- ND (ND + 1) / 2 digit products instead of pw_mulmod's ND^2.
+// Counted with multiplicity a column still has at most ND products below 2^58, so the bound
+// (and the streaming and fold) is pw_mulmod's.
+template <int M, typename ZT>
+__host__ __device__ __forceinline__ void pw_sqrmod(ZT &&Z, int &T, const u64 (&La)[M], int ta)
+{
+    if (ta) {   // 2^N' == -1: the square is 1
+#pragma unroll
+        for (int j = 0; j < M; ++j) Z[j] = j == 0;
+        T = 0;
+        return;
+    }
+    constexpr int DB = 29, ND = (64 * M + DB - 1) / DB;
+    static_assert(ND < 64, "column sums must stay below 2^64");
+    u32 ad[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const int b0 = d * DB, li = b0 >> 6, sh = b0 & 63;
+        u64 x = La[li] >> sh;
+        if (sh + DB > 64 && li + 1 < M) x |= La[li + 1] << (64 - sh);
+        ad[d] = (u32)(x & ((1u << DB) - 1));
+    }
+    u128 acc = 0;          // bits [pos, ...) of the square not yet emitted
+    int pos = 0, k = 0;    // compile-time after unrolling
+    i64 bw = 0;            // borrow of the lo - hi fold
+#pragma clang loop unroll(full)
+    for (int c = 0; c < 2 * ND - 1; ++c) {
+        u64 off = 0;
+        const int i0 = c < ND ? 0 : c - ND + 1;
+#pragma clang loop unroll(full)
+        for (int i = i0; 2 * i < c; ++i) off += (u64)ad[i] * ad[c - i];
+        u64 col = 2 * off;
+        if (!(c & 1)) col += (u64)ad[c / 2] * ad[c / 2];
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(0);   // one column's products live at a time (VGPRs)
+#endif
+        acc += (u128)col << (DB * c - pos);
+        const bool last = c == 2 * ND - 2;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            if (k < 2 * M && (last || DB * (c + 1) - pos >= 64)) {
+                const u64 limb = (u64)acc;
+                acc >>= 64;
+                pos += 64;
+                if (k < M) {
+                    Z[k] = limb;
+                } else {                       // fold: Z[k - M] -= limb (borrow chain)
+                    const u64 z = Z[k - M];
+                    const u64 d1 = z - limb;
+                    i64 b1 = (i64)(d1 > z);
+                    const u64 d2 = d1 + (u64)bw;   // bw <= 0
+                    b1 += bw < 0 ? (i64)(d2 > d1) : 0;
+                    Z[k - M] = d2;
+                    bw = -b1;
+                }
+                ++k;
+            }
+        }
+    }
+    T = (int)bw;   // value = Z + T 2^N', T in {-1, 0}
+}
+
+// inner square of one slot: pw_slot_product with one operand -- the weight (and pw_sqrt2) once,
+// one forward transform, one pw_canon, the squares in R', then the same inverse and un-weighting;
+// leaves the signed coefficients c_t in X and their signs in TT (ends with a barrier).  The
+// stamps keep pw_slot_product's numbering (2 and 3 coincide: there is no second transform).
+template <int M, int LK>
+__device__ __forceinline__ void pw_slot_square(u64 (&La)[M], int Ta, u64 *X, u32 *Xw, int *TT, unsigned *PP, int t,
+                                               unsigned long long *stamp)
+{
+#define PW_STAMP(k) do { if (stamp && t == 0) stamp[k] = __builtin_amdgcn_s_memtime(); } while (0)
+    constexpr int K = 1 << LK, lk = LK;
+    constexpr unsigned NP = 64 * M, N2 = 2 * NP;
+    constexpr unsigned W2 = N2 >> lk;            // omega = 2^W2 (host: K / 2 divides N')
+    static_assert((N2 >> lk) << lk == N2, "omega must be a power of two");
+    int Sa = 0;
+    // negacyclic weight theta^t (pw_slot_product)
+    unsigned Pa = (((unsigned)t * W2) >> 1) + (((W2 & 1) && (t & 1)) ? NP / 4 : 0);   // < N' + N'/4
+    if ((W2 & 1) && (t & 1)) pw_sqrt2<M>(La, Ta);
+    PW_STAMP(1);
+    pw_transform<M, LK, 0>(La, Ta, Sa, Pa, Xw, TT, PP, W2, t);
+    PW_STAMP(2);
+    PW_STAMP(3);
+
+    // ---- inner squares: (2^Pa xa)^2 = 2^(2 Pa) xa^2; the sign flag squares away -------
+    const int ca = pw_canon<M>(La, Ta);
+    u64 Z[M];
+    int Tz, Sz = 0;
+    if (pw_tight(K)) {
+        // through this thread's own LDS word column, as pw_slot_product (the forward transform
+        // ended with an in-wave level; the inverse's first publish comes after)
+        pw_sqrmod<M>(PwLdsZ{Xw + t, K}, Tz, La, ca);
+#pragma unroll
+        for (int j = 0; j < M; ++j) Z[j] = ((u64)Xw[(2 * j + 1) * K + t] << 32) | Xw[2 * j * K + t];
+    } else {
+        pw_sqrmod<M>(Z, Tz, La, ca);
+    }
+    unsigned Pz = pw_mod(2 * Pa, N2);
+    PW_STAMP(4);
+
+    // ---- inverse, then 2^-lk (division by K) and theta^-t: as pw_slot_product -------
+    pw_transform<M, LK, 1>(Z, Tz, Sz, Pz, Xw, TT, PP, W2, t);
+    PW_STAMP(5);
+    if constexpr (PW_UNW_FUSE && !(PW_R4_INV && !pw_tight(K) && LK % 2 == 0)) {
+        const int tf = pw_tight(K) ? pw_launder(t) : t;
+        if ((W2 & 1) && (tf & 1)) pw_sqrt2<M>(Z, Tz);
+    } else {
+        const int tf = pw_tight(K) ? pw_launder(t) : t;
+        const bool halff = (W2 & 1) && (tf & 1);
+        const unsigned un = (((unsigned)tf * W2) >> 1) + lk + (halff ? 1 : 0);   // < N' + lk + 1
+        const unsigned F = pw_mod(Pz + N2 - un + (halff ? NP / 4 : 0), N2);
+        if (halff) pw_sqrt2<M>(Z, Tz);
+        pw_publish<M, LK>(Z, Tz, Sz, Xw, pw_tight(K) ? nullptr : TT, t);
+        pw_wave_sync();                                  // own column only
+        pw_combine<M, LK, pw_pd<M, LK>()>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
+        __syncthreads();                                 // the u64 rows below cross columns
+    }
+    // signed coefficient c_t = v - s p', v in [0, 2^N'], s = (v > 2^(N'-1))
+    const int zt = pw_canon<M>(Z, Tz);
+    const int neg = zt || (Z[M - 1] >> 63);
+    if (pw_tight(K)) {
+        u64 b = (u64)neg;
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            const u64 z = Z[j];
+            X[j * K + t] = z - b;
+            b = b && z == 0;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) X[j * K + t] = Z[j];
+        TT[t] = neg | (zt << 1);                     // s, and limb M of v (2^N' only)
+    }
+    __syncthreads();
+    PW_STAMP(6);
+#undef PW_STAMP
+}
+
+// k_pwsq<M, LK, FUSE>: A[slot] <- A[slot]^2 mod 2^N + 1, one workgroup of K = 2^lk threads per
+// slot: k_pwss without operand B (no second set of pieces, no second forward transform, no
+// pw_late_b: that only keeps two operands' pieces from being live together).  FUSE 0 squares in
+// place; FUSE 1 / 2 take the row DIF's last level(s) on load (slot pairs / quads in k_pwss's
+// XCD-aware order) and write to C.
+template <int M, int LK, int FUSE>
+__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<M, LK>()))) void k_pwsq(u64 *digA, u64 *cbA, int *topA, int l, u64 *digC, u64 *cbC, int *topC,
+                                                  unsigned long long *dbg)
+{
+    unsigned long long *stamp = dbg ? dbg + 8 * (size_t)blockIdx.x : nullptr;
+    if (stamp && threadIdx.x == 0) stamp[0] = __builtin_amdgcn_s_memtime();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int K = 1 << LK;
+    const int t = threadIdx.x;
+    u64 *X = (u64 *)smem;
+    u32 *Xw = (u32 *)smem;
+    int *TT = pw_tight(K) ? nullptr : (int *)(X + (size_t)M * K);
+    unsigned *PP = pw_tight(K) ? nullptr : (unsigned *)(TT + K);
+    int *H = (int *)smem;
+    const int cbw = cb_words(l);
+    constexpr int CLP = pw_piece_limbs<M, LK>();
+    u64 La[M];
+    int Ta = 0;
+    if (FUSE == 0) {
+        const long slot = blockIdx.x;
+        pw_load_piece<M, CLP>(La, Ta, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
+        __syncthreads();   // every piece read before any output limb is written (in place on A)
+        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, PP, t, stamp);
+        pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
+    } else if (FUSE == 2) {
+        const long b = blockIdx.x, nb = gridDim.x, main = nb - nb % 32;
+        long slot = b;
+        if (b < main) {
+            const long x = b & 7, j = b >> 3;
+            slot = 4 * (((j >> 2) << 3) + x) + (j & 3);
+        }
+        const long s0 = slot & ~3L;
+        const int pos = (int)(slot & 3);
+        pw_load_quad_bfly<M, CLP, K, PW_A_INFL>(La, Ta, digA, cbA, topA, s0, pos, l, cbw, t);
+        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, PP, t, stamp);
+        pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
+    } else {
+        const long b = blockIdx.x, nb = gridDim.x, main = nb - nb % 16;
+        long slot = b;
+        if (b < main) {
+            const long x = b & 7, j = b >> 3;
+            slot = 2 * (((j >> 1) << 3) + x) + (j & 1);
+        }
+        pw_load_pair_bfly<M, CLP>(La, Ta, digA, cbA, topA, slot & ~1L, l, cbw, t, slot & 1);
+        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, PP, t, stamp);
+        pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
+    }
+    if (stamp) {
+        __syncthreads();
+        if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();
+    }
+}
