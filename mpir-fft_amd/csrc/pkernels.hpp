@@ -23,7 +23,9 @@
 // (v_add_co / v_addc).  A butterfly partner is read from LDS (limb-major,
 // conflict-free) already rotated by the relative exponent; each thread keeps a
 // *pending* exponent so its own value is never rotated.  The inner products are
-// in-thread product-scanning schoolbook on 32-bit digits (v_mad_u64_u32).
+// in-thread product-scanning on 29/30-bit digits (v_mad_u64_u32): schoolbook, or one
+// Karatsuba level over the N'/2 halves whose fold by 2^N' == -1 is part of the
+// recombination (pw_mulmod; a per-M compile-time switch, pw_kara).
 // The coefficients are then summed (with their signs and the negacyclic wrap) into
 // the l output limbs and stored in the reduced HBM form the inverse pass loads.
 #pragma once
@@ -303,9 +305,238 @@ struct PwLdsZ {
     __device__ __forceinline__ PwLdsRef operator[](int j) const { return PwLdsRef{z + 2 * j * K, K}; }
 };
 
-// z = a b mod p' for canonical a (La, ta), b (Lb, tb); result limbs + top (value = L + T 2^N')
-template <int M, typename ZT>
-__host__ __device__ __forceinline__ void pw_mulmod(ZT &&Z, int &T, const u64 (&La)[M], int ta, const u64 (&Lb)[M], int tb)
+// 32-bit word k of a product sink (registers or PwLdsZ): init writes the words in order (an even
+// word first, so no limb is read before it is whole), put replaces one, get reads one
+template <int M>
+__host__ __device__ __forceinline__ void pw_zword_init(u64 (&Z)[M], int k, u32 w)
+{
+    if (k & 1) Z[k >> 1] |= (u64)w << 32;
+    else Z[k >> 1] = w;
+}
+template <int M>
+__host__ __device__ __forceinline__ void pw_zword_put(u64 (&Z)[M], int k, u32 w)
+{
+    if (k & 1) Z[k >> 1] = (Z[k >> 1] & 0xffffffffull) | ((u64)w << 32);
+    else Z[k >> 1] = (Z[k >> 1] & ~0xffffffffull) | w;
+}
+template <int M>
+__host__ __device__ __forceinline__ u32 pw_zword_get(const u64 (&Z)[M], int k) { return (u32)(Z[k >> 1] >> (32 * (k & 1))); }
+__device__ __forceinline__ void pw_zword_init(const PwLdsZ &Z, int k, u32 w) { Z.z[k * Z.K] = w; }
+__device__ __forceinline__ void pw_zword_put(const PwLdsZ &Z, int k, u32 w) { Z.z[k * Z.K] = w; }
+__device__ __forceinline__ u32 pw_zword_get(const PwLdsZ &Z, int k) { return Z.z[k * Z.K]; }
+
+// ---- Karatsuba over the N'/2 halves (pw_mulmod's main path where pw_kara<M>()) ----------------
+// With X = 2^(N'/2), a = a0 + X a1, b = b0 + X b1 and X^2 = 2^N' == -1, three half products give
+// the residue with the fold already done:
+//   P0 = a0 b0,  P2 = a1 b1,  Ps = (a0 + a1)(b0 + b1),  a0 b1 + a1 b0 = Ps - P0 - P2
+//   a b == (P0 - P2) + X (Ps - P0 - P2)
+//       == [p0l + p0h - p2l + p2h - psh] + X [p0h - p0l - p2l - p2h + psl]      (mod 2^N' + 1)
+// (pXl, pXh: the low N'/2 bits of a product and the rest).  The sums a0 + a1, b0 + b1 (one bit
+// wider than a half, which the half's top digit has room for at every M here) instead of the
+// differences: no signs, so no |.|, no conditional negate and no complement masks in the
+// recombination.  3 ND_h^2 digit products instead of ND^2 (M = 18: 1 200 instead of 1 600).
+
+// the M each form ships at: the form that measured faster; a compile-time switch
+#ifndef PW_KARA_MASK
+#define PW_KARA_MASK 1   // A/B builds: bit 0: M = 18, bit 1: M = 20, bit 2: M = 10
+#endif
+template <int M>
+__host__ __device__ constexpr bool pw_kara()
+{
+    return M % 2 == 0 && ((M == 18 && (PW_KARA_MASK & 1)) || (M == 20 && (PW_KARA_MASK & 2)) || (M == 10 && (PW_KARA_MASK & 4)));
+}
+// digit width of the half products: the widest with ND_h 2^(2 DB) < 2^64 that saves a digit
+template <int M>
+__host__ __device__ constexpr int pw_kara_db() { return M == 10 ? 30 : 29; }
+
+// Where the two half sums (2M words) wait while P0 and P2 are formed: this thread's own word
+// column of the LDS exchange rows (PwParkLds; the rows are idle between the forward transforms'
+// last in-wave level and the inverse's first publish, the argument of pw_slot_product's PwLdsZ
+// branch), or registers (the host build, and callers without a column)
+struct PwParkLds {
+    u32 *z;    // Xw + t
+    int K;
+    __device__ __forceinline__ void put(int k, u32 w) { z[k * K] = w; }
+    __device__ __forceinline__ u32 get(int k) const { return z[k * K]; }
+};
+template <int NW>
+struct PwParkReg {
+    u32 w[NW];
+    __host__ __device__ __forceinline__ void put(int k, u32 v) { w[k] = v; }
+    __host__ __device__ __forceinline__ u32 get(int k) const { return w[k]; }
+};
+
+// the ND DB-bit digits of the value whose 32-bit word i is word(i) (0 past its end)
+template <int DB, int ND, typename W>
+__host__ __device__ __forceinline__ void pw_digits(u32 (&d)[ND], W word)
+{
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+        const int b0 = i * DB, wi = b0 >> 5, sh = b0 & 31;
+        u32 x = word(wi) >> sh;
+        if (sh + DB > 32) x |= word(wi + 1) << (32 - sh);
+        d[i] = x & ((1u << DB) - 1);
+    }
+}
+
+// Half product: the low NW 32-bit words of (sum ad[i] 2^(DB i)) (sum bd[i] 2^(DB i)), product-
+// scanning, handed to sink(k, word) in order k = 0 .. NW - 1 (registers, an add chain or an LDS
+// column: the caller's choice).  A column's excess over its DB-bit digit is the 64-bit addend of
+// the next column's first v_mad_u64_u32 (col >> DB), and the digits are packed into words as
+// they appear: 4 VALU per column beside the products, where a 128-bit accumulator took 8.
+// SQR: the square of ad's value, bd = 2 ad (the doubled digits): every off-diagonal product once,
+// ND (ND + 1) / 2 products; with multiplicity a column still sums at most ND products.
+template <int ND, int DB, int NW, bool SQR = false, typename Sink>
+__host__ __device__ __forceinline__ void pw_halfprod(const u32 (&ad)[ND], const u32 (&bd)[ND], Sink &&sink)
+{
+    // carry-in < 2^(64 - DB) <= 2^(2 DB), at most ND products below 2^(2 DB) each
+    static_assert(DB < 32 && 3 * DB >= 64 && (unsigned long long)(ND + 1) <= (1ull << (64 - 2 * DB)),
+                  "column sums must stay below 2^64");
+    constexpr int NPC = (32 * NW + DB - 1) / DB;   // DB-bit pieces that cover NW words
+    u64 col = 0;
+    u32 cur = 0;
+#pragma clang loop unroll(full)
+    for (int c = 0; c < NPC; ++c) {
+        if (c <= 2 * ND - 2) {
+            const int i0 = c < ND ? 0 : c - ND + 1, i1 = c < ND ? c : ND - 1;
+            if (SQR) {
+#pragma clang loop unroll(full)
+                for (int i = i0; 2 * i < c; ++i) col += (u64)bd[i] * ad[c - i];
+                if (!(c & 1)) col += (u64)ad[c / 2] * ad[c / 2];
+            } else {
+#pragma clang loop unroll(full)
+                for (int i = i0; i <= i1; ++i) col += (u64)ad[i] * bd[c - i];
+            }
+#if defined(__HIP_DEVICE_COMPILE__)
+            __builtin_amdgcn_sched_barrier(0);   // one column's products live at a time (VGPRs)
+#endif
+        }
+        const u32 dg = (u32)col & ((1u << DB) - 1);
+        col >>= DB;
+        const int bits = (c * DB) & 31, k = (c * DB) >> 5;   // bits of word k already in cur
+        cur = bits ? cur | (dg << bits) : dg;
+        if (bits + DB >= 32) {
+            if (k < NW) sink(k, cur);
+            cur = dg >> ((32 - bits) & 31);   // (bits + DB >= 32 with DB < 32: bits > 0)
+        }
+    }
+}
+
+// The Karatsuba recombination's last step: Zw (2M words) + clo X + chi X^2, X = 2^(N'/2), with
+// small signed clo, chi (|clo|, |chi| < 2^30) == Zw + (clo X - chi) mod p'.  One chain over the
+// 2M words adds clo at word M and -chi at word 0 and leaves a top in {-1, 0, 1}; a top of 1 (the
+// words are then small) is folded once more: Zw + 2^N' == Zw - 1, and Zw = 0 gives 2^N' - 1 with
+// top -1.  Returns the top, in {-1, 0}: value == Zw + top 2^N'.
+template <int M>
+__host__ __device__ __forceinline__ int pw_kara_fold(u32 (&Zw)[2 * M], int clo, int chi)
+{
+    const int e0 = chi > 0 ? -1 : 0, d = clo + e0;   // -chi = its M low words + e0 X
+    const u32 x0 = e0 ? ~0u : 0u, x1 = d < 0 ? ~0u : 0u;
+    u32 c = 0;
+#pragma unroll
+    for (int k = 0; k < 2 * M; ++k)
+        Zw[k] = __builtin_addc(Zw[k], k == 0 ? (u32)(-chi) : k < M ? x0 : k == M ? (u32)d : x1, c, &c);
+    int top = (int)c - (d < 0 ? 1 : 0);
+    if (top > 0) {   // rare
+        u32 b = 1;
+#pragma unroll
+        for (int k = 0; k < 2 * M; ++k) Zw[k] = __builtin_subc(Zw[k], 0u, b, &b);
+        top = -(int)b;
+    }
+    return top;
+}
+
+// a b (SQR: a^2, Lb unused) mod p' for limbs below 2^N' by one Karatsuba level (above): the
+// main path of pw_mulmod and pw_sqrmod where pw_kara<M>().  A square runs the same chains on
+// three half squares, so pw_sqrmod(a) and pw_mulmod(a, a) return the same limbs and top.
+template <int M, bool SQR, typename ZT, typename PK>
+__host__ __device__ __forceinline__ void pw_kara_product(ZT &&Z, int &T, const u64 (&La)[M], const u64 (&Lb)[M], PK &park)
+{
+    // The order that keeps the register peak lowest: the half sums first, while La / Lb are
+    // whole, and parked as words; P0 from the low halves into the result words, turned into
+    // (p0l + p0h, p0h - p0l) as its high words appear (its digits die as the result grows); P2
+    // from the high halves, then Ps from the parked sums, their words added and subtracted into
+    // the two running chains as they are emitted.
+    // All chains are 32-bit v_addc / v_subb with explicit carries.
+    constexpr int DB = pw_kara_db<M>(), ND = (32 * M + 1 + DB - 1) / DB;   // digits of a half sum
+    static_assert(ND == (32 * M + DB - 1) / DB, "the half sums' extra bit must not cost a digit");
+    auto wa = [&](int i) -> u32 { return (u32)(La[i >> 1] >> (32 * (i & 1))); };
+    auto wb = [&](int i) -> u32 { return (u32)(Lb[i >> 1] >> (32 * (i & 1))); };
+    u32 sca = 0, scb = 0;   // the sums' bit N'/2
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        park.put(k, __builtin_addc(wa(k), wa(M + k), sca, &sca));
+        if (!SQR) park.put(M + k, __builtin_addc(wb(k), wb(M + k), scb, &scb));
+    }
+    u32 ad[ND], bd[ND];
+    // the second factor's digits: b's, or for a square the doubled digits of a (pw_halfprod SQR)
+    auto second = [&](auto word) {
+        if constexpr (SQR) {
+#pragma unroll
+            for (int i = 0; i < ND; ++i) bd[i] = 2 * ad[i];
+        } else {
+            pw_digits<DB, ND>(bd, word);
+        }
+    };
+    u32 Zw[2 * M];   // words 0 .. M-1: the low chain, M .. 2M-1: the high chain
+    int clo = 0, chi = 0;   // their signed carries (weights 2^(N'/2), 2^N' over the chain's base)
+    pw_digits<DB, ND>(ad, [&](int i) -> u32 { return i < M ? wa(i) : 0u; });
+    second([&](int i) -> u32 { return i < M ? wb(i) : 0u; });
+    {
+        u32 c = 0, b = 0;
+        pw_halfprod<ND, DB, 2 * M, SQR>(ad, bd, [&](int k, u32 w) {
+            if (k < M) {
+                Zw[k] = w;
+            } else {
+                const u32 lo = Zw[k - M];
+                Zw[k - M] = __builtin_addc(lo, w, c, &c);   // p0l + p0h
+                Zw[k] = __builtin_subc(w, lo, b, &b);       // p0h - p0l
+            }
+        });
+        clo += (int)c;
+        chi -= (int)b;
+    }
+    pw_digits<DB, ND>(ad, [&](int i) -> u32 { return i < M ? wa(M + i) : 0u; });
+    second([&](int i) -> u32 { return i < M ? wb(M + i) : 0u; });
+    {
+        u32 b1 = 0, b2 = 0, c3 = 0, b4 = 0;
+        pw_halfprod<ND, DB, 2 * M, SQR>(ad, bd, [&](int k, u32 w) {
+            if (k < M) {   // - p2l in both
+                Zw[k] = __builtin_subc(Zw[k], w, b1, &b1);
+                Zw[M + k] = __builtin_subc(Zw[M + k], w, b2, &b2);
+            } else {       // + p2h low, - p2h high
+                Zw[k - M] = __builtin_addc(Zw[k - M], w, c3, &c3);
+                Zw[k] = __builtin_subc(Zw[k], w, b4, &b4);
+            }
+        });
+        clo += (int)c3 - (int)b1;
+        chi -= (int)b2 + (int)b4;
+    }
+    pw_digits<DB, ND>(ad, [&](int i) -> u32 { return i < M ? park.get(i) : i == M ? sca : 0u; });
+    second([&](int i) -> u32 { return i < M ? park.get(M + i) : i == M ? scb : 0u; });
+    {
+        u32 c = 0, b = 0;   // Ps < 2^(N' + 2): 2M + 1 words
+        pw_halfprod<ND, DB, 2 * M + 1, SQR>(ad, bd, [&](int k, u32 w) {
+            if (k < M) Zw[M + k] = __builtin_addc(Zw[M + k], w, c, &c);        // + psl high
+            else if (k < 2 * M) Zw[k - M] = __builtin_subc(Zw[k - M], w, b, &b);   // - psh low
+            else clo -= (int)w;   // psh's word M: straight into the low chain's carry
+        });
+        clo -= (int)b;
+        chi += (int)c;
+    }
+    const int top = pw_kara_fold<M>(Zw, clo, chi);
+#pragma unroll
+    for (int j = 0; j < M; ++j) Z[j] = ((u64)Zw[2 * j + 1] << 32) | Zw[2 * j];
+    T = top;   // in {-1, 0}: the schoolbook path's contract
+}
+
+// z = a b mod p' for canonical a (La, ta), b (Lb, tb); result limbs + top (value = L + T 2^N'),
+// T in {-1, 0} from either path (the Karatsuba recombination folds its halves' small signed
+// carries back into the words).
+// park: where the Karatsuba path keeps the half sums (PwParkLds / PwParkReg)
+template <int M, typename ZT, typename PK = PwParkReg<2 * M>>
+__host__ __device__ __forceinline__ void pw_mulmod(ZT &&Z, int &T, const u64 (&La)[M], int ta, const u64 (&Lb)[M], int tb,
+                                                   PK park = PK{})
 {
     if (ta | tb) {   // 2^N' == -1: the product is 1, -b or -a  (cf. mul_fft.c:3250)
         if (ta && tb) {
@@ -325,59 +556,24 @@ __host__ __device__ __forceinline__ void pw_mulmod(ZT &&Z, int &T, const u64 (&L
         T = -1 + (int)(i64)acc;
         return;
     }
-    // Full product over 29-bit digits: a column sums at most ND < 64 products < 2^58,
-    // so one v_mad_u64_u32 per digit product with no carry tracking.  Columns are
-    // streamed into 64-bit limbs and folded on the fly: Z = lo - hi (2^N' == -1).
+    if constexpr (pw_kara<M>()) {
+        pw_kara_product<M, false>(Z, T, La, Lb, park);
+        return;
+    }
+    // Full product over 29-bit digits: a column sums at most ND < 64 products < 2^58, so one
+    // v_mad_u64_u32 per digit product with no carry tracking (pw_halfprod over the whole
+    // operands).  The 4M product words are folded on the fly: Z = lo - hi (2^N' == -1), the low
+    // 2M words stored, the high 2M subtracted from them in one borrow chain.
     constexpr int DB = 29, ND = (64 * M + DB - 1) / DB;
-    static_assert(ND < 64, "column sums must stay below 2^64");
     u32 ad[ND], bd[ND];
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        const int b0 = d * DB, li = b0 >> 6, sh = b0 & 63;
-        u64 x = La[li] >> sh, y = Lb[li] >> sh;
-        if (sh + DB > 64 && li + 1 < M) {
-            x |= La[li + 1] << (64 - sh);
-            y |= Lb[li + 1] << (64 - sh);
-        }
-        ad[d] = (u32)(x & ((1u << DB) - 1));
-        bd[d] = (u32)(y & ((1u << DB) - 1));
-    }
-    u128 acc = 0;          // bits [pos, ...) of the product not yet emitted
-    int pos = 0, k = 0;    // compile-time after unrolling
-    i64 bw = 0;            // borrow of the lo - hi fold
-#pragma clang loop unroll(full)
-    for (int c = 0; c < 2 * ND - 1; ++c) {
-        u64 col = 0;
-        const int i0 = c < ND ? 0 : c - ND + 1, i1 = c < ND ? c : ND - 1;
-#pragma clang loop unroll(full)
-        for (int i = i0; i <= i1; ++i) col += (u64)ad[i] * bd[c - i];
-#if defined(__HIP_DEVICE_COMPILE__)
-        __builtin_amdgcn_sched_barrier(0);   // one column's products live at a time (VGPRs)
-#endif
-        acc += (u128)col << (DB * c - pos);
-        const bool last = c == 2 * ND - 2;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            if (k < 2 * M && (last || DB * (c + 1) - pos >= 64)) {
-                const u64 limb = (u64)acc;
-                acc >>= 64;
-                pos += 64;
-                if (k < M) {
-                    Z[k] = limb;
-                } else {                       // fold: Z[k - M] -= limb (borrow chain)
-                    const u64 z = Z[k - M];
-                    const u64 d1 = z - limb;
-                    i64 b1 = (i64)(d1 > z);
-                    const u64 d2 = d1 + (u64)bw;   // bw <= 0
-                    b1 += bw < 0 ? (i64)(d2 > d1) : 0;
-                    Z[k - M] = d2;
-                    bw = -b1;
-                }
-                ++k;
-            }
-        }
-    }
-    T = (int)bw;   // value = Z + T 2^N', T in {-1, 0}
+    pw_digits<DB, ND>(ad, [&](int i) -> u32 { return i < 2 * M ? (u32)(La[i >> 1] >> (32 * (i & 1))) : 0u; });
+    pw_digits<DB, ND>(bd, [&](int i) -> u32 { return i < 2 * M ? (u32)(Lb[i >> 1] >> (32 * (i & 1))) : 0u; });
+    u32 bw = 0;
+    pw_halfprod<ND, DB, 4 * M>(ad, bd, [&](int k, u32 w) {
+        if (k < 2 * M) pw_zword_init(Z, k, w);
+        else pw_zword_put(Z, k - 2 * M, __builtin_subc(pw_zword_get(Z, k - 2 * M), w, bw, &bw));
+    });
+    T = -(int)bw;   // value = Z + T 2^N', T in {-1, 0}
 }
 
 // exchange: thread t publishes its value as words (normalised first: pw_norm) and, unless
@@ -948,7 +1144,11 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
     const int ca = pw_canon<M>(La, Ta), cb = pw_canon<M>(Lb, Tb);
     u64 Z[M];
     int Tz, Sz = Sa ^ Sb;
-    if (pw_tight(K)) {
+    if constexpr (pw_kara<M>()) {
+        // Karatsuba: the half sums are parked in this thread's own LDS word column (the argument
+        // below), the result's limbs stay in registers (half as many digits are live)
+        pw_mulmod<M>(Z, Tz, La, ca, Lb, cb, PwParkLds{Xw + t, K});
+    } else if (pw_tight(K)) {
         // the product's limbs through this thread's own LDS word column (B's transform ended
         // with an in-wave level: no other wave reads this column; the inverse's first publish
         // comes after): C4 pointwise 40.5 -> 40.0 ms, its spills 128 -> 84 B per lane; at
@@ -1200,15 +1400,21 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
 // z = a^2 mod p' for canonical a (La, ta); result limbs + top (value = L + T 2^N').
 // One digit array: column c sums the products ad[i] ad[c - i], i < c - i, once and doubles the
 // sum, plus ad[c/2]^2 for even c -- ND (ND + 1) / 2 digit products instead of pw_mulmod's ND^2.
-// Counted with multiplicity a column still has at most ND products below 2^58, so the bound
-// (and the streaming and fold) is pw_mulmod's.
-template <int M, typename ZT>
-__host__ __device__ __forceinline__ void pw_sqrmod(ZT &&Z, int &T, const u64 (&La)[M], int ta)
+// Counted with multiplicity a column still has at most ND products below 2^58: the bound of
+// pw_mulmod's schoolbook, and the same lo - hi fold (the same limbs and top as pw_mulmod(a, a)).
+// Where pw_kara<M>() it takes pw_mulmod's Karatsuba routine instead, as three half squares.
+// park: as pw_mulmod's
+template <int M, typename ZT, typename PK = PwParkReg<2 * M>>
+__host__ __device__ __forceinline__ void pw_sqrmod(ZT &&Z, int &T, const u64 (&La)[M], int ta, PK park = PK{})
 {
     if (ta) {   // 2^N' == -1: the square is 1
 #pragma unroll
         for (int j = 0; j < M; ++j) Z[j] = j == 0;
         T = 0;
+        return;
+    }
+    if constexpr (pw_kara<M>()) {   // three half squares; the same chains as pw_mulmod(a, a), so the same limbs
+        pw_kara_product<M, true>(Z, T, La, La, park);
         return;
     }
     constexpr int DB = 29, ND = (64 * M + DB - 1) / DB;
@@ -1287,7 +1493,9 @@ __device__ __forceinline__ void pw_slot_square(u64 (&La)[M], int Ta, u64 *X, u32
     const int ca = pw_canon<M>(La, Ta);
     u64 Z[M];
     int Tz, Sz = 0;
-    if (pw_tight(K)) {
+    if constexpr (pw_kara<M>()) {
+        pw_sqrmod<M>(Z, Tz, La, ca, PwParkLds{Xw + t, K});   // as pw_slot_product's Karatsuba branch
+    } else if (pw_tight(K)) {
         // through this thread's own LDS word column, as pw_slot_product (the forward transform
         // ended with an in-wave level; the inverse's first publish comes after)
         pw_sqrmod<M>(PwLdsZ{Xw + t, K}, Tz, La, ca);
