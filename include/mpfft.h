@@ -139,6 +139,15 @@ int mpfft_workspace_layout(long n1, long n2, unsigned long depth, unsigned long 
  * inverse doubles not yet doubled -- into the product; MPFFT_EUNSUPPORTED on plans that do not
  * fold (mpfft_stage_kernels names k_combine_red for them) */
 #define MPFFT_STAGE_FOLD_COMBINE 7
+/* (tests) or-ed onto MPFFT_STAGE_INV_ROWS, _INV_COLUMNS or _SCALE: the stage runs as the whole
+ * multiply drives it (Exec::drive_single) instead of in the stand-alone stage mode -- on fold plans
+ * 2^-(depth+1) rides in the last inverse row pass, or with the inverse MFA twiddle in the first
+ * pass of each column block; the truncated inverse leaves its top-level doubling of rows
+ * [dbl_lo, dbl_hi) undone, and SCALE (a no-op on fold plans) applies it.  After driven INV_ROWS and
+ * INV_COLUMNS a fold plan's slots are what MPFFT_STAGE_FOLD_COMBINE reads; on the other plans
+ * driven INV_ROWS, INV_COLUMNS, SCALE leave the canonical coefficients.  MPFFT_EINVAL on any other
+ * stage. */
+#define MPFFT_STAGE_DRIVEN 0x100
 int mpfft_stage(int stage, const uint64_t *d_i1, const uint64_t *d_i2, uint64_t *d_r, long n1, long n2,
                 unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
 

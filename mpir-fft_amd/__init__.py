@@ -27,6 +27,8 @@ _lib = None
 
 STAGE_FWD_COLUMNS, STAGE_FWD_ROWS, STAGE_POINTWISE, STAGE_INV_ROWS, STAGE_INV_COLUMNS, \
     STAGE_SCALE, STAGE_COMBINE, STAGE_FOLD_COMBINE = range(8)
+# (tests) or-ed onto STAGE_INV_ROWS / _INV_COLUMNS / _SCALE: the stage as the whole multiply drives it
+STAGE_DRIVEN = 0x100
 
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p

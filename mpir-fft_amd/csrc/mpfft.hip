@@ -339,10 +339,18 @@ static void layout_out(const Plan &P, size_t *out)
 static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const uint64_t *d_i2, uint64_t *d_r,
                         void *d_ws, size_t ws_bytes, void *stream)
 {
+    const bool driven = (stage & MPFFT_STAGE_DRIVEN) != 0;   // (tests) the inverse stages as run_all drives them
+    stage &= ~MPFFT_STAGE_DRIVEN;
+    if (driven && stage != MPFFT_STAGE_INV_ROWS && stage != MPFFT_STAGE_INV_COLUMNS && stage != MPFFT_STAGE_SCALE)
+        return MPFFT_EINVAL;
     if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
     (void)hipGetLastError();
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
+    if (driven) {
+        X.drive_single();
+        if (stage == MPFFT_STAGE_SCALE) plan_dbl(P, &X.dbl_lo, &X.dbl_hi);
+    }
     switch (stage) {
     case MPFFT_STAGE_FWD_COLUMNS: return X.fwd_columns(d_i1, P.n1, d_i2, P.n2, fwd_nops(P), fwd_op(P));
     case MPFFT_STAGE_FWD_ROWS: return X.fwd_rows(fwd_nops(P), fwd_op(P));

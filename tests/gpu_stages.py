@@ -8,6 +8,7 @@ Stage specs:
            X_k = sum_j x_j 2^(w j k) (a3 output spec, up to the reference's two
            revbin permutations which this build never performs), p < T/NC
   pointwise slot = XA * XB mod 2^N + 1, reduced form (limbs + carry masks) (a20)
+  (after the forward columns and after the inverse rows alone: tests/stage_model.py's U and V)
   inverse  slot j = c_j = sum_i a_i b_(j-i), exact, j < trunc           (a13, a21)
   combine  r = i1 * i2                                                  (a22)
 """
@@ -19,6 +20,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
+import stage_model  # noqa: E402
 from helpers import chunks, log2, revbin, to_int  # noqa: E402
 
 
@@ -79,7 +81,7 @@ def _convolution(ca, cb, N, T, mul=None):
     return [(C >> (j * S)) & mask for j in range(T)]
 
 
-def run_stages(mp, depth, w, a, b, dev="cuda:0", check=("fwd", "pw", "inv", "comb"), mul=None):
+def run_stages(mp, depth, w, a, b, dev="cuda:0", check=("fwdc", "fwd", "pw", "invr", "inv", "comb"), mul=None):
     """Returns a list of failure strings (empty = all stages exact)."""
     import torch
     n1, n2 = len(a), len(b)
@@ -106,9 +108,25 @@ def run_stages(mp, depth, w, a, b, dev="cuda:0", check=("fwd", "pw", "inv", "com
             if xj:
                 e = (w * j * k) % (2 * N)
                 acc += xj << e if e < N else -(xj << (e - N))
-        return acc % p
+        return stage_model.modp(acc, N)   # (folding at 2^N == -1: a plain % p is a quadratic division)
 
     mp.stage(mp.STAGE_FWD_COLUMNS, da, db, dr, n1, n2, depth, w, ws)
+    if "fwdc" in check:
+        # the forward columns alone (tests/stage_model.py): live rows p < Tr, reduced form
+        torch.cuda.synchronize()
+        S = stage_model.Shape(P, depth, w)
+        for which, x in ((0, xa), (1, xb)):
+            dig, top = _slots(mp, ws, n1, n2, depth, w, which)
+            cbx = _cbs(mp, ws, n1, n2, depth, w, which)
+            U = stage_model.fwd_columns(x, S)
+            for pp in range(Tr):
+                for c in range(NC):
+                    s = pp * NC + c
+                    got = stage_model.unpack_value(dig[s], top[s], cbx[s], N) % p
+                    if got != U[pp][c]:
+                        fails.append(f"fwd columns op{which} slot ({pp},{c}): got {got:x} top {top[s]} want {U[pp][c]:x}")
+                        if len(fails) > 8:
+                            return fails
     mp.stage(mp.STAGE_FWD_ROWS, da, db, dr, n1, n2, depth, w, ws)
     torch.cuda.synchronize()
     XA, XB = {}, {}
@@ -134,13 +152,29 @@ def run_stages(mp, depth, w, a, b, dev="cuda:0", check=("fwd", "pw", "inv", "com
         dig, top = _slots(mp, ws, n1, n2, depth, w, 0)
         cbA = _cbs(mp, ws, n1, n2, depth, w, 0)
         for s in range(T):
-            want = XA[s] * XB[s] % p
+            want = stage_model.modp(XA[s] * XB[s], N)
             got = _val_reduced(dig, top, cbA, s, N) % p    # reduced form (what the inverse pass loads)
             if got != want:
                 fails.append(f"pointwise slot {s}: got {got:x} (top {top[s]}) want {want:x}")
                 if len(fails) > 8:
                     return fails
-    for st in (mp.STAGE_INV_ROWS, mp.STAGE_INV_COLUMNS, mp.STAGE_SCALE):
+    mp.stage(mp.STAGE_INV_ROWS, da, db, dr, n1, n2, depth, w, ws)
+    if "invr" in check:
+        # the inverse rows alone: the unnormalised row inverse of the pointwise products, un-twiddled
+        torch.cuda.synchronize()
+        S = stage_model.Shape(P, depth, w)
+        dig, top = _slots(mp, ws, n1, n2, depth, w, 0)
+        cbA = _cbs(mp, ws, n1, n2, depth, w, 0)
+        V = stage_model.inv_rows([[stage_model.modp(XA[pp * NC + q] * XB[pp * NC + q], N) for q in range(NC)] for pp in range(Tr)], S)
+        for pp in range(Tr):
+            for c in range(NC):
+                s = pp * NC + c
+                got = stage_model.unpack_value(dig[s], top[s], cbA[s], N) % p
+                if got != V[pp][c]:
+                    fails.append(f"inverse rows slot ({pp},{c}): got {got:x} top {top[s]} want {V[pp][c]:x}")
+                    if len(fails) > 8:
+                        return fails
+    for st in (mp.STAGE_INV_COLUMNS, mp.STAGE_SCALE):
         mp.stage(st, da, db, dr, n1, n2, depth, w, ws)
     torch.cuda.synchronize()
     if "inv" in check:

@@ -69,6 +69,22 @@ def test_invalid_parameters_rejected(mp):
         mp.plan_info(10, 10, 5, 3)
 
 
+def test_driven_stage_flag_is_validated(mp):
+    """MPFFT_STAGE_DRIVEN goes with the three inverse stages only: any other stage is refused before
+    anything is touched (null pointers: an accepted stage gets as far as the workspace check)"""
+    src = open(os.path.join(ROOT, "include", "mpfft.h")).read()
+    assert re.search(r"#define MPFFT_STAGE_DRIVEN 0x100\b", src) and mp.STAGE_DRIVEN == 0x100
+    lib = mp.lib()
+    EINVAL, ENOMEM = 1, 4
+    ok = (mp.STAGE_INV_ROWS, mp.STAGE_INV_COLUMNS, mp.STAGE_SCALE)
+    for st in range(8):
+        want = ENOMEM if st in ok else EINVAL
+        assert lib.mpfft_stage(st | mp.STAGE_DRIVEN, None, None, None, 300, 300, 10, 3, None, 0, None) == want, st
+        assert lib.mpfft_sqr_stage(st | mp.STAGE_DRIVEN, None, None, 300, 10, 3, None, 0, None) == want, st
+        assert lib.mpfft_stage(st, None, None, None, 300, 300, 10, 3, None, 0, None) == ENOMEM, st
+    assert lib.mpfft_stage(8 | mp.STAGE_DRIVEN, None, None, None, 300, 300, 10, 3, None, 0, None) == EINVAL
+
+
 def test_compute_fails_loudly_without_gpu(mp):
     import torch
     if torch.cuda.is_available():
