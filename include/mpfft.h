@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 3
+#define MPFFT_VERSION 4
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -104,6 +104,54 @@ int mpfft_sqr_stage(int stage, const uint64_t *d_a, uint64_t *d_r, long n, unsig
 /* As mpfft_stage_kernels(n, n, ...), the pointwise field "k_pwsq<M>..." on nested plans and
  * "<kernel> (B = A)" where a multiply kernel runs with A's arrays as both operands. */
 int mpfft_sqr_stage_kernels(long n, unsigned long depth, unsigned long w, char *buf, size_t len);
+
+/* ---- products mod 2^B + 1 (MPFFT_VERSION 4): r = a b mod M, M = 2^B + 1, B = 64 L, as a
+ * length-2n negacyclic convolution mod 2^N + 1 (n = 2^depth, N = n w) of bits1 = B / 2n bit
+ * pieces, weighted by the 4n-th root of unity sqrt2^w (the reference's fft_mulmod_2expp1,
+ * mul_fft.c:2998-3167): half the slots of the full product at the same coefficient size, and
+ * L + 1 limbs over the bus instead of 2 L.
+ * Operands and result are L + 1 limbs, fully reduced: 0 <= a <= 2^B, the top limb 0 or 1 and the
+ * low L limbs 0 when it is 1 (the host entries return MPFFT_EINVAL otherwise; the device entries
+ * do not look).  r may not overlap a or b; d_r may be the next call's operand.
+ * Valid (L, depth, w): 2 <= depth <= 30, 64 | N, 2n | 64 L (MPFFT_EINVAL otherwise);
+ * 2 bits1 + depth + 2 <= N, so that the signed coefficients can be read back (MPFFT_ETOOBIG);
+ * N / 64 <= 4096 (MPFFT_EUNSUPPORTED).  mpfft_mulmod_next_size gives an efficient L.
+ * Limits: a negacyclic transform cannot be truncated, so with power-of-two w the fully
+ * efficient moduli lie a factor 2 apart (B ~ n^2 w); for B a power of two (Fermat numbers) the
+ * pieces are N/4 bits, not N/2, and the slot count equals that of the multiply-and-fold route
+ * (the reference's low-limb CRT trick, which would close that gap, is not implemented).
+ * Not covered: mod 2^B - 1, the sqrt2 front end, the sharded / multi-GPU entries and
+ * mpfft_set_devices routing -- these always run on the calling thread's device. */
+int mpfft_mulmod_check_params(long L, unsigned long depth, unsigned long w);
+int mpfft_mulmod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w);
+/* One operand split, weighted and transformed once; k_pwsq on the nested plans. */
+int mpfft_sqrmod_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w);
+/* Device-resident, queued on `stream` and not synchronised; d_ws holds
+ * mpfft_mulmod_workspace_bytes(L, depth, w, sqr) bytes and need not be cleared. */
+int mpfft_mulmod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                        unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+int mpfft_sqrmod_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                        void *d_ws, size_t ws_bytes, void *stream);
+size_t mpfft_mulmod_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr);
+/* out[10] as mpfft_plan_info: j1 = j2 = trunc = 2n, bits1 = 64 L / 2n. */
+int mpfft_mulmod_plan_info(long L, unsigned long depth, unsigned long w, long *out);
+/* out[8] as mpfft_workspace_layout (sqr: entries 3..5 are 0). */
+int mpfft_mulmod_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out);
+/* One stage on the mulmod workspace (tests).  MPFFT_STAGE_FWD_COLUMNS: the split + weight launch
+ * and the column transform; MPFFT_STAGE_SCALE: the un-weight (slot j by theta^-j 2^-(depth+1),
+ * canonical); MPFFT_STAGE_COMBINE: the negacyclic combine of the canonical coefficients into
+ * d_r (L + 1 limbs); the others are the multiply's.  MPFFT_STAGE_DRIVEN and
+ * MPFFT_STAGE_FOLD_COMBINE return MPFFT_EINVAL. */
+int mpfft_mulmod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                       unsigned long depth, unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream);
+/* As mpfft_stage_kernels; the fwd_columns, scale and combine fields name the negacyclic kernels. */
+int mpfft_mulmod_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len);
+/* The valid (depth, w) of least predicted time for this L (mpfft_choose's candidates and cost
+ * model at 2n slots), MPFFT_ETOOBIG if none is valid. */
+int mpfft_mulmod_choose(long L, unsigned long *depth, unsigned long *w);
+/* For a caller free to choose the modulus: every candidate's smallest valid L >= min_L (a
+ * multiple of its granularity 2n / 64), and of those the (L, depth, w) of least predicted time. */
+int mpfft_mulmod_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity
@@ -304,7 +352,9 @@ int mpfft_set_devices(int ngpus, const int *devices, long min_l);
 int mpfft_last_ngpus(void);
 
 /* Stage profiling of the whole-multiply entries (new_mpn_mul, mpfft_mul_ex,
- * mpfft_mul_device, and the squares mpfft_sqr_ex / mpfft_sqr_device): between begin and end, each of the next max_calls multiplies
+ * mpfft_mul_device, the squares mpfft_sqr_ex / mpfft_sqr_device, and the products mod 2^B + 1, where
+ * the weight launch counts with the forward columns, the un-weight is the scale stage and the
+ * negacyclic combine the combine stage): between begin and end, each of the next max_calls multiplies
  * records a HIP event on its own stream at every stage boundary (no other change to
  * the work); end synchronises and returns the summed per-stage milliseconds
  * (stage_ms[MPFFT_NSTAGES], MPFFT_STAGE_* order) and the number of profiled calls. */

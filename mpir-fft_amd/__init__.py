@@ -183,6 +183,33 @@ def lib():
             h.mpfft_sqr_stage.restype = ctypes.c_int
             h.mpfft_sqr_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_char_p, ctypes.c_size_t]
             h.mpfft_sqr_stage_kernels.restype = ctypes.c_int
+        if hasattr(h, "mpfft_mulmod_ex"):   # MPFFT_VERSION 4 (older libraries in A/B runs lack them)
+            _ulp = ctypes.POINTER(ctypes.c_ulong)
+            h.mpfft_mulmod_check_params.argtypes = [_L, _UL, _UL]
+            h.mpfft_mulmod_check_params.restype = ctypes.c_int
+            h.mpfft_mulmod_ex.argtypes = [_u64p, _u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_mulmod_ex.restype = ctypes.c_int
+            h.mpfft_sqrmod_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_sqrmod_ex.restype = ctypes.c_int
+            h.mpfft_mulmod_device.argtypes = [_vp, _vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
+            h.mpfft_mulmod_device.restype = ctypes.c_int
+            h.mpfft_sqrmod_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
+            h.mpfft_sqrmod_device.restype = ctypes.c_int
+            h.mpfft_mulmod_workspace_bytes.argtypes = [_L, _UL, _UL, ctypes.c_int]
+            h.mpfft_mulmod_workspace_bytes.restype = ctypes.c_size_t
+            h.mpfft_mulmod_plan_info.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
+            h.mpfft_mulmod_plan_info.restype = ctypes.c_int
+            h.mpfft_mulmod_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+            h.mpfft_mulmod_workspace_layout.restype = ctypes.c_int
+            h.mpfft_mulmod_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _UL, _UL, ctypes.c_int, _vp,
+                                             ctypes.c_size_t, _vp]
+            h.mpfft_mulmod_stage.restype = ctypes.c_int
+            h.mpfft_mulmod_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+            h.mpfft_mulmod_stage_kernels.restype = ctypes.c_int
+            h.mpfft_mulmod_choose.argtypes = [_L, _ulp, _ulp]
+            h.mpfft_mulmod_choose.restype = ctypes.c_int
+            h.mpfft_mulmod_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
+            h.mpfft_mulmod_next_size.restype = ctypes.c_int
         _lib = h
     return _lib
 
@@ -496,6 +523,134 @@ def sqr_workspace_views(ws, n, depth, w):
     dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
     top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
     return dig, top
+
+
+# ---- products mod 2^B + 1, B = 64 L (mpfft_mulmod_*, include/mpfft.h): operands and result are
+# L + 1 limbs, fully reduced (0 <= a <= 2^B) ----
+
+def mulmod_check_params(L, depth, w):
+    return lib().mpfft_mulmod_check_params(L, depth, w)
+
+
+def mulmod(a, b, depth, w):
+    """a b mod 2^(64 L) + 1 for L + 1-limb fully reduced a, b: a new uint64 array of L + 1 limbs."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if len(a) != len(b) or len(a) < 2:
+        raise ValueError("operands are L + 1 limbs each")
+    L = len(a) - 1
+    r = np.zeros(L + 1, dtype=np.uint64)
+    rc = lib().mpfft_mulmod_ex(_p(r), _p(a), _p(b), L, depth, w)
+    if rc:
+        raise MpfftError(rc, f"mulmod(L={L}, depth={depth}, w={w})")
+    return r
+
+
+def sqrmod(a, depth, w):
+    """a^2 mod 2^(64 L) + 1 (one forward transform)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if len(a) < 2:
+        raise ValueError("the operand is L + 1 limbs")
+    L = len(a) - 1
+    r = np.zeros(L + 1, dtype=np.uint64)
+    rc = lib().mpfft_sqrmod_ex(_p(r), _p(a), L, depth, w)
+    if rc:
+        raise MpfftError(rc, f"sqrmod(L={L}, depth={depth}, w={w})")
+    return r
+
+
+def mulmod_workspace_bytes(L, depth, w, sqr=False):
+    return int(lib().mpfft_mulmod_workspace_bytes(L, depth, w, int(bool(sqr))))
+
+
+def alloc_workspace_mulmod(L, depth, w, sqr=False, device="cuda"):
+    import torch
+    nb = mulmod_workspace_bytes(L, depth, w, sqr)
+    if nb == 0:
+        raise MpfftError(mulmod_check_params(L, depth, w), "mulmod workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def mulmod_device(d_r, d_a, d_b, L, depth, w, ws, stream=None):
+    """d_r[:L+1] = d_a d_b mod 2^(64 L) + 1 on the GPU; queued on `stream`, not synchronised.
+    d_r may not be an operand (it may be the next call's)."""
+    rc = lib().mpfft_mulmod_device(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws),
+                                   ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmod_device")
+
+
+def sqrmod_device(d_r, d_a, L, depth, w, ws, stream=None):
+    rc = lib().mpfft_sqrmod_device(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws),
+                                   ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_sqrmod_device")
+
+
+def mulmod_plan_info(L, depth, w):
+    out = (ctypes.c_long * 10)()
+    rc = lib().mpfft_mulmod_plan_info(L, depth, w, out)
+    if rc:
+        raise MpfftError(rc, f"mulmod plan(L={L}, depth={depth}, w={w})")
+    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
+    return dict(zip(keys, list(out)))
+
+
+def mulmod_workspace_layout(L, depth, w, sqr=False):
+    out = (ctypes.c_size_t * 8)()
+    rc = lib().mpfft_mulmod_workspace_layout(L, depth, w, int(bool(sqr)), out)
+    if rc:
+        raise MpfftError(rc, "mulmod_workspace_layout")
+    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
+    return dict(zip(keys, list(out)))
+
+
+def mulmod_workspace_views(ws, L, depth, w, sqr=False):
+    """(digA, topA, cbA) views into a mulmod workspace tensor (slot-major): limbs (slots, l) int64,
+    carry limbs int32, carry masks (slots, cbw) int64."""
+    import torch
+    P = mulmod_plan_info(L, depth, w)
+    lay = mulmod_workspace_layout(L, depth, w, sqr)
+    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
+    u8 = ws.view(torch.uint8)
+    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
+    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
+    cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
+    return dig, top, cb
+
+
+def mulmod_stage(which, d_a, d_b, d_r, L, depth, w, ws, sqr=False, stream=None):
+    rc = lib().mpfft_mulmod_stage(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, int(bool(sqr)), _ptr(ws),
+                                  ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_mulmod_stage({which})")
+
+
+def mulmod_stage_kernels(L, depth, w, sqr=False):
+    """dict stage -> the kernel a product mod 2^(64 L) + 1 launches for it"""
+    buf = ctypes.create_string_buffer(512)
+    rc = lib().mpfft_mulmod_stage_kernels(L, depth, w, int(bool(sqr)), buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmod_stage_kernels")
+    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+
+
+def mulmod_choose(L):
+    """(depth, w) of least predicted time that are valid for this L."""
+    d, w = ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_mulmod_choose(L, ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"mulmod_choose(L={L})")
+    return int(d.value), int(w.value)
+
+
+def mulmod_next_size(min_L):
+    """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
+    L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_mulmod_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"mulmod_next_size({min_L})")
+    return int(L.value), int(d.value), int(w.value)
 
 
 # ---- sharded (multi-GPU) stages: see sharded.py ------------------------------

@@ -919,8 +919,9 @@ struct Exec {
         return scale_rows(dbl_hi, P.Tr, e);
     }
 
-    // rows [r0_, r1_) by 2^e; with rpass, rows [d0, d1) inside them by 2^(e+1)
-    int scale_rows(long r0_, long r1_, u64 e, long d0 = 0, long d1 = 0)
+    // rows [r0_, r1_) by 2^e; with rpass, rows [d0, d1) inside them by 2^(e+1), and slot j of
+    // the launch by 2^(e - j estep) (estep != 0: unweight())
+    int scale_rows(long r0_, long r1_, u64 e, long d0 = 0, long d1 = 0, u64 estep = 0)
     {
         const long cnt = (r1_ - r0_) * ccount, s0 = r0_ * ccount;
         if (cnt <= 0) return MPFFT_OK;
@@ -938,8 +939,9 @@ struct Exec {
             if (!f) return MPFFT_EUNSUPPORTED;
             const unsigned lo = (unsigned)((d0 - r0_) * ccount), hi = (unsigned)((d1 - r0_) * ccount);
             return launch(f, dim3((unsigned)cnt), dim3(snt), rp_scale_lds((int)P.l), dig, cbp, top, (unsigned)P.N,
-                          (unsigned)e, (unsigned)(e + 1), d1 > d0 ? lo : 0u, d1 > d0 ? hi : 0u);
+                          (unsigned)e, (unsigned)(e + 1), d1 > d0 ? lo : 0u, d1 > d0 ? hi : 0u, (unsigned)estep);
         }
+        if (estep) return MPFFT_EINVAL;   // the per-slot exponent is k_rscale's alone
         if (P.wave)
             return launch(wv_fns(P.wU, P.wfull).scale, dim3((unsigned)((cnt + WPB - 1) / WPB)), dim3(64 * WPB),
                           (size_t)WPB * 16 * P.l, dig, cbp, top, (int)P.l, P.N, e, cnt);
@@ -1038,5 +1040,97 @@ struct Exec {
         a.G = 1;
         a.S = 1;
         return combine1(a, 1, P.total, r, st, zflags == st, nullptr);
+    }
+
+    // ---- the negacyclic top level (nega.hpp) on a make_plan_mod plan ----------------------
+    // the shape of its slot-wise kernels, as the sqrt2 top level's: l = 2048 runs four limbs per
+    // thread over 512 threads (two over 1024 spill)
+    int nega_u() const { return P.U == 2 && P.l == 2048 ? 4 : P.U; }
+    int nega_tpb() const { return nega_u() != P.U ? 512 : P.tpb; }
+    size_t nega_lds() const { return lds_bytes((int)P.l, s2_rb(nega_u()), 3, nega_u(), nega_tpb() / 64); }
+
+    NegaArgs nega_args() const
+    {
+        NegaArgs a;
+        memset(&a, 0, sizeof(a));
+        for (int k = 0; k < 2; ++k) {
+            a.dig[k] = col.dig[k];
+            a.cb[k] = col.cb[k];
+            a.top[k] = col.top[k];
+        }
+        a.L = P.n1;
+        a.bits1 = P.bits1;
+        a.N = P.N;
+        a.w = (u64)P.w;
+        a.l = (int)P.l;
+        a.depth = P.depth;
+        return a;
+    }
+
+    // words of both combine flag regions from comb_flags() on (the weight launch clears them)
+    static long nega_flag_words(const Plan &P) { return (long)((P.off_nflags - P.off_flags) / 4) + nega_blocks(P.n1) + 2; }
+
+    // split + weight: slot j <- theta^j piece j of each operand (nops 1: operand 0 alone)
+    int nweight(const u64 *srcA, const u64 *srcB, int nops)
+    {
+        NegaArgs a = nega_args();
+        a.src[0] = srcA;
+        a.src[1] = srcB;
+        a.zp = zflags;
+        a.zn = zflags_n;
+        void (*f)(NegaArgs) = nullptr;
+        switch (nega_u()) {
+        case 1: f = k_nweight<1>; break;
+        case 2: f = k_nweight<2>; break;
+        case 4: f = k_nweight<4>; break;
+        }
+        if (!f) return MPFFT_EUNSUPPORTED;
+        return launch(f, dim3((unsigned)(2 * P.n), (unsigned)nops), dim3(nega_tpb()), nega_lds(), a);
+    }
+
+    // un-weight + scaling: slot j <- theta^-j 2^-(depth+1) slot j, canonical.  Register-pass
+    // plans with even w: k_rscale with the exponent taken from the slot index; else k_nunweight
+    bool unweight_rscale() const { return P.rpass && P.w % 2 == 0; }
+    int unweight()
+    {
+        if (unweight_rscale()) return scale_rows(0, P.NR, 2 * P.N - (u64)(P.depth + 1), 0, 0, (u64)P.w / 2);
+        const NegaArgs a = nega_args();
+        void (*f)(NegaArgs) = nullptr;
+        switch (nega_u()) {
+        case 1: f = k_nunweight<1>; break;
+        case 2: f = k_nunweight<2>; break;
+        case 4: f = k_nunweight<4>; break;
+        }
+        if (!f) return MPFFT_EUNSUPPORTED;
+        return launch(f, dim3((unsigned)(2 * P.n)), dim3(nega_tpb()), nega_lds(), a);
+    }
+
+    // negacyclic combine: k_combine1 into the scratch, k_nwrap, k_nfix; r: L + 1 limbs
+    int ncombine(u64 *r, unsigned char *ws)
+    {
+        u64 *T = (u64 *)(ws + P.off_nscr);
+        u32 *st = (u32 *)(ws + P.off_nflags);
+        const bool cleared = zflags == comb_flags(ws);
+        int rc = combine_single(T, ws);
+        if (rc) return rc;
+        NegaCombArgs a;
+        memset(&a, 0, sizeof(a));
+        a.T = T;
+        a.TL = P.total;
+        a.dig = row.dig[0];
+        a.top = row.top[0];
+        a.l = (int)P.l;
+        a.N = P.N;
+        a.bits1 = P.bits1;
+        a.L = P.n1;
+        a.len = P.len;
+        a.nT = (int)((P.total + P.n1 - 1) / P.n1);
+        a.qmax = (int)(((u64)(P.len - 1) * P.bits1 + P.N) / (64 * (u64)P.n1));
+        a.K = 2u * (u32)(a.nT / 2 + 1 + a.qmax / 2 + 1);
+        a.inv_bits1 = 1.0 / (double)P.bits1;
+        a.nblk = nega_blocks(P.n1);
+        if (!cleared) HIPCHK(hipMemsetAsync(st, 0, (size_t)(a.nblk + 2) * 4, s));
+        if ((rc = launch(k_nwrap<NEGA_V>, dim3((unsigned)a.nblk), dim3(256), 0, a, r, st))) return rc;
+        return launch(k_nfix, dim3(1), dim3(1024), 0, r, (long)P.n1, (const u32 *)st, a.nblk);
     }
 };

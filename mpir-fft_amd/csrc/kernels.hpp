@@ -405,17 +405,19 @@ struct S2Args {
 };
 
 // x[1] <- z^m x[1] (x[2] scratch): m w even: 2^(m w / 2); odd: 2^((m w - 1)/2) sqrt2 (FFT_twiddle_sqrt2 :972)
+// add (< 2N): a further factor 2^add in the same rotation (the negacyclic un-weight's scaling)
 template <int U>
-__device__ __forceinline__ void s2_root(const WG &c, i64 (&x)[3][2 * U], u64 m, u64 w, u64 N, int l, i64 *stage, int rb)
+__device__ __forceinline__ void s2_root(const WG &c, i64 (&x)[3][2 * U], u64 m, u64 w, u64 N, int l, i64 *stage, int rb,
+                                        u64 add = 0)
 {
     const u64 N2 = 2 * N, mw = m * w;
     u64 ee[3] = {0, 0, 0};
     if (!(mw & 1)) {
-        ee[1] = (mw / 2) % N2;
+        ee[1] = (mw / 2 + add) % N2;
         rotate_set<U, 3>(c, x, ee, N, l, stage, rb);
         return;
     }
-    const u64 e = (mw - 1) / 2;
+    const u64 e = (mw - 1) / 2 + add;
 #pragma unroll
     for (int q = 0; q < 2 * U; ++q) x[2][q] = x[1][q];
     ee[1] = (e + 3 * N / 4) % N2;

@@ -33,6 +33,7 @@
 #include "kernels.hpp"
 #include "combine.hpp"
 #include "fold.hpp"
+#include "nega.hpp"
 #include "wdispatch.hpp"
 #include "bdispatch.hpp"
 #include "pdispatch.hpp"
@@ -240,6 +241,38 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
     return rc;
 }
 
+// The product mod 2^B + 1 on a make_plan_mod plan (nega.hpp): split + weight, the multiply's
+// untruncated stages (the columns take slots, not operands), un-weight + scaling, negacyclic
+// combine.  d_a, d_b: L + 1 limbs, fully reduced; d_r: L + 1 limbs.  Stage events as run_all's:
+// the weight launch counts with the columns, the un-weight is the scaling stage.
+static int run_all_mod(const Plan &P, u64 *d_r, const u64 *d_a, const u64 *d_b, unsigned char *ws, hipStream_t s)
+{
+    Exec X(P, s);
+    X.single(ws);
+    X.zflags = X.comb_flags(ws);   // cleared by the weight launch, with k_nwrap's behind them
+    X.zflags_n = Exec::nega_flag_words(P);
+    X.fuse_row_last = true;
+    ProfCall pc;
+    int rc;
+    pc.mark(0, s);
+    if ((rc = X.nweight(d_a, d_b, fwd_nops(P)))) return rc;
+    if ((rc = X.fwd_columns(nullptr, 0, nullptr, 0, fwd_nops(P), fwd_op(P)))) return rc;
+    pc.mark(1, s);
+    if ((rc = X.fwd_rows(fwd_nops(P), fwd_op(P)))) return rc;
+    pc.mark(2, s);
+    if ((rc = X.pointwise())) return rc;   // a fused pointwise leaves X's views on C
+    pc.mark(3, s);
+    if ((rc = X.inv_rows())) return rc;
+    pc.mark(4, s);
+    if ((rc = X.itft(0, P.NR, P.NR))) return rc;
+    pc.mark(5, s);
+    if ((rc = X.unweight())) return rc;
+    pc.mark(6, s);
+    rc = X.ncombine(d_r, ws);
+    pc.mark(7, s);
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -310,6 +343,15 @@ static std::string stage_kernel_names(const Plan &P)
         snprintf(fwdc, sizeof fwdc, "%s (split: k_rpass<%d,%d,0,2>)", pass, fg, fp);
     else
         snprintf(fwdc, sizeof fwdc, "%s", pass);
+    if (P.nega) {   // the negacyclic top level's own launches (nega.hpp)
+        Exec X(P, nullptr);
+        char unw[64];
+        snprintf(fwdc, sizeof fwdc, "k_nweight<%d> (split + weight) + %s", X.nega_u(), pass);
+        if (X.unweight_rscale()) snprintf(unw, sizeof unw, "k_rscale (un-weight: exponent per slot)");
+        else snprintf(unw, sizeof unw, "k_nunweight<%d>", X.nega_u());
+        return std::string(fwdc) + ';' + rows + ';' + pw + ';' + pass + ';' + invc + ';' + unw + ';'
+               + "k_combine1 + k_nwrap + k_nfix (negacyclic)";
+    }
     return std::string(fwdc) + ';' + rows + ';' + pw + ';' + pass + ';' + invc + ';' + scale + ';' + comb;
 }
 
@@ -448,8 +490,10 @@ const char *mpfft_strerror(int code)
 {
     switch (code) {
     case MPFFT_OK: return "ok";
-    case MPFFT_EINVAL: return "invalid parameters (need n1,n2 >= 1, 2 <= depth <= 30, n*w % 64 == 0)";
-    case MPFFT_ETOOBIG: return "operands too large for the convolution: need j1 + j2 - 1 <= 2^(depth+1)";
+    case MPFFT_EINVAL: return "invalid parameters (need n1,n2 >= 1, 2 <= depth <= 30, n*w % 64 == 0)"
+                              "; mod 2^B+1: L >= 1, 2^(depth+1) | 64 L, operands fully reduced";
+    case MPFFT_ETOOBIG: return "operands too large for the convolution: need j1 + j2 - 1 <= 2^(depth+1)"
+                               "; mod 2^B+1: 2 bits1 + depth + 2 <= n*w, bits1 = 64 L / 2^(depth+1)";
     case MPFFT_EUNSUPPORTED: return "coefficient size n*w/64 > 4096 limbs is not supported";
     case MPFFT_ENOMEM: return "device allocation failed";
     case MPFFT_EHIP: return hipGetErrorString(last_hip_error);
@@ -870,6 +914,181 @@ int mpfft_sqr_ex(uint64_t *r, const uint64_t *a, long n, unsigned long depth, un
     if ((rc = mul_host(P, r, a, n, a, n))) return rc;
     g_last_ngpus = 1;
     return MPFFT_OK;
+}
+
+// ---- products mod 2^B + 1 (nega.hpp, make_plan_mod, run_all_mod).  Out of scope as for the
+// squares: the sqrt2 front end, the sharded and multi-GPU entries, mpfft_set_devices routing. --
+int mpfft_mulmod_check_params(long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_mod(&P, L, depth, w, false);
+}
+
+size_t mpfft_mulmod_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr)
+{
+    Plan P;
+    if (make_plan_mod(&P, L, depth, w, sqr != 0)) return 0;
+    return P.bytes;
+}
+
+int mpfft_mulmod_plan_info(long L, unsigned long depth, unsigned long w, long *out)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, false);
+    if (rc) return rc;
+    plan_info_out(P, out);
+    return MPFFT_OK;
+}
+
+int mpfft_mulmod_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, sqr != 0);
+    if (rc) return rc;
+    layout_out(P, out);
+    return MPFFT_OK;
+}
+
+int mpfft_mulmod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                        unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, false);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (d_r == d_a || d_r == d_b) return MPFFT_EINVAL;
+    (void)hipGetLastError();
+    return run_all_mod(P, d_r, d_a, d_b, (unsigned char *)d_ws, (hipStream_t)stream);
+}
+
+int mpfft_sqrmod_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                        void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, true);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (d_r == d_a) return MPFFT_EINVAL;
+    (void)hipGetLastError();
+    return run_all_mod(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream);
+}
+
+int mpfft_mulmod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                       unsigned long depth, unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, sqr != 0);
+    if (rc) return rc;
+    if ((stage & MPFFT_STAGE_DRIVEN) || stage == MPFFT_STAGE_FOLD_COMBINE) return MPFFT_EINVAL;
+    if (stage != MPFFT_STAGE_FWD_COLUMNS && stage != MPFFT_STAGE_SCALE && stage != MPFFT_STAGE_COMBINE)
+        return single_stage(P, stage, d_a, sqr ? d_a : d_b, d_r, d_ws, ws_bytes, stream);   // the multiply's, Tr = NR
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    Exec X(P, (hipStream_t)stream);
+    X.single((unsigned char *)d_ws);
+    if (stage == MPFFT_STAGE_SCALE) return X.unweight();
+    if (stage == MPFFT_STAGE_COMBINE) return X.ncombine(d_r, (unsigned char *)d_ws);
+    if ((rc = X.nweight(d_a, sqr ? d_a : d_b, fwd_nops(P)))) return rc;
+    return X.fwd_columns(nullptr, 0, nullptr, 0, fwd_nops(P), fwd_op(P));
+}
+
+int mpfft_mulmod_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, sqr != 0);
+    if (rc) return rc;
+    return copy_out(stage_kernel_names(P), buf, len);
+}
+
+// fully reduced: the top limb 0, or 1 over L zero limbs
+static bool mod_reduced(const uint64_t *a, long L)
+{
+    if (a[L] == 0) return true;
+    if (a[L] != 1) return false;
+    for (long i = 0; i < L; ++i)
+        if (a[i]) return false;
+    return true;
+}
+
+// host operands on the calling thread's device (as mul_host): io holds a, b and r, L + 1 limbs each
+static int mulmod_host(const Plan &P, uint64_t *r, const uint64_t *a, const uint64_t *b)
+{
+    const long L = P.n1;
+    if (!mod_reduced(a, L) || (!P.sqr && !mod_reduced(b, L))) return MPFFT_EINVAL;
+    int rc;
+    (void)hipGetLastError();
+    int ndev = 0, dev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
+    DevCtx &C = g_dev[dev];
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
+    const size_t nb = (size_t)(L + 1) * 8;
+    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, 3 * nb))) return rc;
+    u64 *d_a = C.io, *d_b = P.sqr ? d_a : d_a + (L + 1), *d_r = C.io + 2 * (L + 1);
+    HIPCHK(hipMemcpyAsync(d_a, a, nb, hipMemcpyHostToDevice, C.stream));
+    if (!P.sqr) HIPCHK(hipMemcpyAsync(d_b, b, nb, hipMemcpyHostToDevice, C.stream));
+    if ((rc = run_all_mod(P, d_r, d_a, d_b, C.ws, C.stream))) return rc;
+    HIPCHK(hipMemcpyAsync(r, d_r, nb, hipMemcpyDeviceToHost, C.stream));
+    HIPCHK(hipStreamSynchronize(C.stream));
+    g_last_ngpus = 1;
+    return MPFFT_OK;
+}
+
+int mpfft_mulmod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, false);
+    if (rc) return rc;
+    return mulmod_host(P, r, a, b);
+}
+
+int mpfft_sqrmod_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_mod(&P, L, depth, w, true);
+    if (rc) return rc;
+    return mulmod_host(P, r, a, a);
+}
+
+// mpfft_choose's candidates; a candidate's cost is choose_cost at its 2n slots, whatever L.
+// fixed_L > 0: the candidates valid for that L; else each candidate at its smallest valid
+// L >= min_L (a multiple of its granularity 2n / 64)
+static int mulmod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w)
+{
+    double best = -1.0;
+    for (unsigned long d = 2; d <= 24; ++d)
+        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
+            const unsigned long long N = (1ull << d) * wv;
+            if (N % 64) continue;
+            if (N / 64 > 4096) break;
+            const long g = std::max<long>(1, (2L << d) / 64);
+            const long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
+            Plan P;
+            if (make_plan_mod(&P, Lc, d, wv, false)) continue;
+            const double c = choose_cost(P);
+            if (best < 0 || c < best) {
+                best = c;
+                *L = Lc;
+                *depth = d;
+                *w = wv;
+            }
+        }
+    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+}
+
+int mpfft_mulmod_choose(long L, unsigned long *depth, unsigned long *w)
+{
+    long Lc = 0;
+    if (L < 1) return MPFFT_EINVAL;
+    return mulmod_pick(L, 0, &Lc, depth, w);
+}
+
+int mpfft_mulmod_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w)
+{
+    if (min_L < 1) return MPFFT_EINVAL;
+    return mulmod_pick(0, min_L, L, depth, w);
 }
 
 // release the calling device's cached workspace (the next call re-allocates)

@@ -67,6 +67,11 @@ struct Plan {
     int fuse_rows;      // row DIF levels that run inside the pointwise: 1 (slot pairs), 2 (slot quads), 0
     size_t off_digC, off_topC, off_cbC;
     bool sqr;           // squaring plan (make_plan_sqr): one operand, no B arrays in the layout
+    // make_plan_mod: a product mod 2^(64 n1) + 1 as a length-2n negacyclic convolution (nega.hpp)
+    bool nega;
+    size_t off_nflags;  // k_nwrap's look-back flags, ticket counter and overflow word (behind off_flags:
+                        // the weight launch clears both in one range)
+    size_t off_nscr;    // the unsigned sum of the canonical coefficients (k_combine1's output), `total` limbs
 };
 
 static int ilog2(long v) { int d = 0; while ((1L << d) < v) ++d; return d; }
@@ -326,13 +331,10 @@ static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned lo
     return MPFFT_OK;
 }
 
-// Squaring plan: the multiply's plan for n by n limbs -- the same split, trunc, fold, ltw and
-// fuse_rows -- with operand B's arrays (dig + top + cbb of make_plan_split) taken out of the
-// layout: everything behind them moves down by their size.
-static int make_plan_sqr(Plan *p, long n, unsigned long depth, unsigned long w)
+// operand B's arrays (dig + top + cbb of make_plan_split) out of a plan's layout: everything
+// behind them moves down by their size
+static void plan_drop_b(Plan *p)
 {
-    const int rc = make_plan(p, n, n, depth, w);
-    if (rc) return rc;
     const size_t b = (p->has_c ? p->off_digC : p->off_flags) - p->off_digB;
     p->sqr = true;
     p->off_digB = p->off_topB = p->off_cbB = 0;
@@ -344,6 +346,58 @@ static int make_plan_sqr(Plan *p, long n, unsigned long depth, unsigned long w)
     p->off_flags -= b;
     p->off_meta -= b;
     p->bytes -= b;
+}
+
+// Squaring plan: the multiply's plan for n by n limbs -- the same split, trunc, fold, ltw and
+// fuse_rows -- with operand B's arrays taken out of the layout.
+static int make_plan_sqr(Plan *p, long n, unsigned long depth, unsigned long w)
+{
+    const int rc = make_plan(p, n, n, depth, w);
+    if (rc) return rc;
+    plan_drop_b(p);
+    return MPFFT_OK;
+}
+
+// Negacyclic plan (nega.hpp): a b mod 2^B + 1, B = 64 L, as the length-2n negacyclic convolution
+// of bits1 = B / 2n bit pieces.  The multiply's kernel families and its split for an
+// untruncated transform of these (depth, w) (make_plan's choice at Tr = NR); nothing is
+// truncated (a weighted transform cannot be), no fold, no fused scaling: the un-weight is the
+// scaling pass.  The signed coefficients need 2 bits1 + depth + 2 <= N.
+static u64 nega_scratch_limbs(const Plan &P) { return ((u64)(2 * P.n - 1) * P.bits1 + P.N + 1 + 63) / 64; }
+static const int NEGA_V = 4;   // k_nwrap: limbs per thread, 256 threads
+static long nega_blocks(long L) { return (L + 256 * NEGA_V - 1) / (256 * NEGA_V); }
+
+static int make_plan_mod(Plan *p, long L, unsigned long depth, unsigned long w, bool sqr)
+{
+    memset(p, 0, sizeof(*p));
+    if (L < 1 || depth < 2 || depth > 30 || w < 1 || w > 4096) return MPFFT_EINVAL;
+    const u64 n2 = (u64)2 << depth, N = ((u64)1 << depth) * w, B = 64 * (u64)L;
+    if (N % 64 || B % n2) return MPFFT_EINVAL;
+    if (N / 64 > 4096) return MPFFT_EUNSUPPORTED;
+    const u64 b = B / n2;
+    if (2 * b + depth + 2 > N) return MPFFT_ETOOBIG;
+    int rc = make_plan_split(p, 1, 1, depth, w, false, -1);
+    if (rc) return rc;
+    if (p->rpass && (p->l == 2048 || p->l == 4096)) {   // make_plan's split where nothing is truncated
+        Plan q;
+        if (make_plan_split(&q, 1, 1, depth, w, false, (int)depth / 2 + 1, p->l == 2048) == MPFFT_OK && q.rpass) *p = q;
+    }
+    p->nega = true;
+    p->n1 = p->n2 = L;
+    p->bits1 = b;
+    p->j1 = p->j2 = p->len = p->trunc = 2 * p->n;
+    p->Tr = p->NR;
+    p->fold = 0;
+    p->ltw = false;
+    p->fuse_scale = false;
+    p->total = (long)nega_scratch_limbs(*p);
+    if (sqr) plan_drop_b(p);
+    size_t o = p->off_flags;
+    o += align_up((size_t)(p->total / 256 + 8) * 4, 256);
+    p->off_nflags = o; o += align_up((size_t)(nega_blocks(L) + 2) * 4, 256);
+    p->off_meta = o; o += align_up((size_t)p->slots * 4, 256);
+    p->off_nscr = o; o += align_up((size_t)p->total * 8, 256);
+    p->bytes = o;
     return MPFFT_OK;
 }
 

@@ -1323,10 +1323,14 @@ __device__ int rp_canon_par(const BSlot &b, int l, int wave, int lane, int *scr)
 // mpn_normmod_2expp1 :272) by all eight waves, one segment each (rp_canon_par);
 // the canonical residue in [0, 2^N] is stored with zero carry masks and its carry limb.
 // Coefficients [lo, hi) of the launch take exponent e2 instead of e (one launch for all rows).
+// estep != 0: coefficient j of the launch takes e - j estep (the negacyclic un-weight theta^-j,
+// theta = 2^estep, with the scaling; the host keeps j estep <= e).
 template <int PP, int NT = RP_NT>
-__global__ __launch_bounds__(NT) void k_rscale(u64 *dig, u64 *cb, int *top, u32 N, u32 e, u32 e2, u32 lo, u32 hi)
+__global__ __launch_bounds__(NT) void k_rscale(u64 *dig, u64 *cb, int *top, u32 N, u32 e, u32 e2, u32 lo, u32 hi,
+                                               u32 estep)
 {
     if (blockIdx.x >= lo && blockIdx.x < hi) e = e2;   // itft's deferred doubling: those rows by 2^-depth
+    e -= blockIdx.x * estep;
     constexpr int l = 1024 * PP, HP = l / 2, cbw = 2 * l / 64, R = rp_r(PP, NT);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const RX<PP> X{smem};

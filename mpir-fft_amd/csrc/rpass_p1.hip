@@ -85,13 +85,13 @@ rp_pair_fn rp_pair_get(int l, int op)
     return nullptr;
 }
 
-void (*rp_scale_get_p1(int nt))(u64 *, u64 *, int *, u32, u32, u32, u32, u32)
+void (*rp_scale_get_p1(int nt))(u64 *, u64 *, int *, u32, u32, u32, u32, u32, u32)
 {
     return nt == 256 ? k_rscale<1, 256> : k_rscale<1>;
 }
 
-void (*rp_scale_get_p2(int nt))(u64 *, u64 *, int *, u32, u32, u32, u32, u32);
-void (*rp_scale_get_p4(int nt))(u64 *, u64 *, int *, u32, u32, u32, u32, u32);
+void (*rp_scale_get_p2(int nt))(u64 *, u64 *, int *, u32, u32, u32, u32, u32, u32);
+void (*rp_scale_get_p4(int nt))(u64 *, u64 *, int *, u32, u32, u32, u32, u32, u32);
 
 rp_scale_fn rp_scale_get(int l, int nt)
 {
