@@ -33,8 +33,10 @@
 #include "coeff.hpp"
 
 // LDS of one k_pwss workgroup: M K limbs (the exchange rows, then the coefficients; the l
-// output overflows alias them) + tops + pending exponents.  C3 (M = 18, K = 256): 38 912 B,
-// so four workgroups share a CU's 160 KiB (pw_wpe).
+// output overflows alias them) + three more exchange rows of K words (rows 2M .. 2M+2: the
+// complements of rows 0 .. 2, pw_group) + one K-word array of tops and pending exponents
+// (pw_pack_tp).  C3 (M = 18, K = 256): 40 960 B, exactly a quarter of a CU's 160 KiB, so four
+// workgroups share it (pw_wpe).
 // Tight form (PW_TIGHT9, K = 512): no top / pending-exponent arrays beside the exchange rows --
 // a level's partner tops and exponents go by a wave shuffle (partner in the wave) or through
 // the first two exchange rows before the words are published (two more barriers), and the
@@ -64,9 +66,28 @@ __host__ __device__ constexpr bool pw_late_b(int K) { return pw_tight(K) || PW_L
 #define PW_QUAD4 0        // A/B builds: the quad loader's four inputs in flight at once
 #endif
 
+// Grouped wrap selects (pw_combine GRP): the exchange has GRP - 1 rows more, rows 2M .. 2M+GRP-2
+// = ~rows 0 .. GRP-2, so a reader takes the wrap test, the base select and the mask select once
+// per GRP consecutive words (6 VALU per word -> 4.5 at GRP = 2 -> 3.75 at GRP = 4).  Not in the
+// tight form: its 80 KiB have no room for a row, it keeps the per-word form.  GRP = 4 (three rows)
+// fits four workgroups per CU only with the tops and pending exponents packed into one K-word
+// array (pw_pack_tp).  C3, ms per multiply: 7.13-7.16 per word, 6.85-6.90 in pairs, 6.78-6.80 in
+// fours (profiles/r12/pw_pair_ab.txt).
+#ifndef PW_GROUP
+#define PW_GROUP 4        // A/B builds: 1 the per-word form, rows [0, 2M) only; 2 pairs, one row more
+#endif
+static_assert(PW_GROUP == 1 || PW_GROUP == 2 || PW_GROUP == 4, "group sizes built");
+__host__ __device__ constexpr int pw_group(int K) { return pw_tight(K) ? 1 : PW_GROUP; }
+// tops and pending exponents in one word per thread, (2 T + S) << 12 | P  (P < 2 N' < 2^12; the
+// tops are a few units: pw_norm, pw_sqrt2)
+__host__ __device__ constexpr bool pw_pack_tp(int K) { return pw_group(K) == 4; }
+// 32-bit words of the exchange rows ahead of the tops (TT) and pending exponents (PP)
+__host__ __device__ constexpr size_t pw_row_words(int M, int K) { return (size_t)(2 * M + pw_group(K) - 1) * K; }
+
 __host__ __device__ constexpr size_t pw_lds_bytes(int M, int K, int l)
 {
-    return ((size_t)M * K * 8 > (size_t)l * 4 ? (size_t)M * K * 8 : (size_t)l * 4) + (pw_tight(K) ? 0 : (size_t)K * 8);
+    return (pw_row_words(M, K) * 4 > (size_t)l * 4 ? pw_row_words(M, K) * 4 : (size_t)l * 4) +
+           (pw_tight(K) ? 0 : pw_pack_tp(K) ? (size_t)K * 4 : (size_t)K * 8);
 }
 
 // waves per SIMD k_pwss is compiled for: 4 (VGPRs <= 128) where the LDS fits 1024 threads per
@@ -88,7 +109,8 @@ template <int M, int LK>
 __host__ __device__ constexpr int pw_pd() { return pw_wpe<M, LK>() == 4 ? (pw_tight(1 << LK) ? PW_PD_TIGHT : PW_PD_WIDE) : 2 * M; }
 
 // Exchange format: thread t publishes its value as 2M 32-bit words, word k at
-// Xw[k K + t] (conflict-free for any rotation), top in TT[t].  Before publishing,
+// Xw[k K + t] (conflict-free for any rotation), top in TT[t]; where pw_group(K) = G > 1, also the
+// complements of words 0 .. G-2 at rows 2M .. 2M+G-2.  Before publishing,
 // pw_norm moves the top to -1 (almost always exactly): the reader's rotation then
 // needs no correction term, only a complement mask and one carry chain.
 
@@ -146,12 +168,19 @@ __host__ __device__ __forceinline__ int pw_norm(u64 (&L)[M], int T)
 // FIXE >= 0: the caller guarantees E mod N' == FIXE, so the rotation is a compile-time constant
 // and every wrap test, word address and complement mask below folds away (the forward
 // transforms' first level, where E is exactly N'/2 for every thread: pw_transform)
-template <int M, int LK, int PD = 2 * M, int FIXE = -1>
+// GRP = 2: the caller guarantees row 2M of the partner's column holds ~w_0 (pw_publish_words where
+// pw_group(K) = 2).  Words k, k + 1 (k even) then share the wrap test of k: in stream order the pair
+// straddles the wrap only when k + 1 == Yw, its second word is row 0 read plain -- which is row
+// 2M (same base as row 2M - 1) under the wrapped mask, ~w_0 ^ ~smask = w_0 ^ smask.  One compare
+// and two selects per pair instead of per word; w_(-1) stays on its own.  GRP = 4: the same with
+// rows 2M .. 2M+2 = ~w_0 .. ~w_2 and words k .. k + 3 (k a multiple of 4) sharing the test of k.
+template <int M, int LK, int PD = 2 * M, int FIXE = -1, int GRP = 1>
 __host__ __device__ __forceinline__ void pw_combine(u64 (&L)[M], int &T, int &S, int alpha, const u32 *Xw,
                                                    int packed, int q, unsigned E)
 {
     constexpr int K = 1 << LK, NW = 2 * M;
     constexpr unsigned NP = 64 * M;
+    static_assert(GRP == 1 || GRP == 2 || GRP == 4, "group sizes built");
     const int Tq = packed >> 1, Sq = packed & 1;
     bool neg = E >= NP;
     if (neg) E -= NP;
@@ -181,7 +210,7 @@ __host__ __device__ __forceinline__ void pw_combine(u64 (&L)[M], int &T, int &S,
     u32 wv[NW];
 #pragma unroll
     for (int k = 0; k < D0; ++k) {
-        const bool wr = k < Yw;
+        const bool wr = (k & ~(GRP - 1)) < Yw;
         wv[k] = (wr ? bw : bn)[k * K];
 #if defined(__HIP_DEVICE_COMPILE__)
         if ((k & 7) == 7) __builtin_amdgcn_sched_barrier(0);
@@ -190,10 +219,10 @@ __host__ __device__ __forceinline__ void pw_combine(u64 (&L)[M], int &T, int &S,
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
         if (k + D0 < NW) {
-            const bool wr2 = k + D0 < Yw;
+            const bool wr2 = ((k + D0) & ~(GRP - 1)) < Yw;
             wv[k + D0] = (wr2 ? bw : bn)[(k + D0) * K];
         }
-        const bool wr = k < Yw;
+        const bool wr = (k & ~(GRP - 1)) < Yw;
         const u32 w = wv[k] ^ (wr ? ~smask : smask);
 #if defined(__HIP_DEVICE_COMPILE__)
         const u32 o = __builtin_amdgcn_alignbit(w, wprev, sh);
@@ -591,6 +620,12 @@ __device__ __forceinline__ void pw_publish_words(const u64 (&L)[M], u32 *Xw, int
         col[(2 * j) * K] = (u32)L[j];
         col[(2 * j + 1) * K] = (u32)(L[j] >> 32);
     }
+    // rows 2M .. (pw_combine GRP)
+    if constexpr (pw_group(K) >= 2) col[2 * M * K] = ~(u32)L[0];
+    if constexpr (pw_group(K) == 4) {
+        col[(2 * M + 1) * K] = ~(u32)(L[0] >> 32);
+        col[(2 * M + 2) * K] = ~(u32)L[1];
+    }
 }
 
 template <int M, int LK>
@@ -725,11 +760,20 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
         pw_publish_words<M, LK>(L, Xw, t);
         if (cross) __syncthreads(); else pw_wave_sync();
     } else {
-        pw_publish<M, LK>(L, T, S, Xw, TT, t);
-        PP[t] = P;
-        if (cross) __syncthreads(); else pw_wave_sync();
-        Pq = PP[q];
-        packed = TT[q];
+        if constexpr (pw_pack_tp(K)) {
+            pw_publish<M, LK>(L, T, S, Xw, nullptr, t);
+            TT[t] = (int)((unsigned)(2 * T + S) << 12 | P);
+            if (cross) __syncthreads(); else pw_wave_sync();
+            const int tp = TT[q];
+            Pq = (unsigned)tp & 4095u;
+            packed = tp >> 12;
+        } else {
+            pw_publish<M, LK>(L, T, S, Xw, TT, t);
+            PP[t] = P;
+            if (cross) __syncthreads(); else pw_wave_sync();
+            Pq = PP[q];
+            packed = TT[q];
+        }
     }
     const int own_packed = 2 * T + S;   // (UNW) as published: T normalised by pw_publish / pw_norm
     unsigned E;
@@ -744,7 +788,7 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
             const unsigned Eu = (unsigned)__builtin_amdgcn_readfirstlane((int)Em);   // wave-uniform (above)
             pw_combine_fixed<M, LK, FIXJ>(L, T, S, top ? 1 : -1, Xw, packed, q, E, Eu);
         } else {
-            pw_combine<M, LK, pw_pd<M, LK>()>(L, T, S, top ? 1 : -1, Xw, packed, q, E);
+            pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(L, T, S, top ? 1 : -1, Xw, packed, q, E);
         }
         if (!top) P = pw_mod(P + tw, N2);
     } else {
@@ -756,12 +800,12 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
             const unsigned F = pw_unweight_exp<M, LK>(P, W2, pw_tight(K) ? pw_launder(t) : t);
             constexpr unsigned NP = 64 * M;
             const unsigned Eq = pw_mod(E + F, N2);
-            pw_combine<M, LK, pw_pd<M, LK>()>(L, T, S, 0, Xw, own_packed, t, top ? F : pw_mod(F + NP, N2));
+            pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(L, T, S, 0, Xw, own_packed, t, top ? F : pw_mod(F + NP, N2));
             __builtin_amdgcn_sched_barrier(0);   // the two rotated reads one after the other
-            pw_combine<M, LK, pw_pd<M, LK>()>(L, T, S, 1, Xw, packed, q, Eq);
+            pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(L, T, S, 1, Xw, packed, q, Eq);
             P = 0;
         } else {
-            pw_combine<M, LK, pw_pd<M, LK>()>(L, T, S, top ? 1 : -1, Xw, packed, q, E);
+            pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(L, T, S, top ? 1 : -1, Xw, packed, q, E);
             if (!top) P = pw_mod(P + N2 - tw, N2);
         }
     }
@@ -784,7 +828,7 @@ __device__ __forceinline__ void pw_level4_dit(u64 (&L)[M], int &T, int &S, unsig
 {
     constexpr int K = 1 << LK;
     constexpr unsigned NP = 64 * M, N2 = 2 * NP;
-    static_assert(!pw_tight(K), "the radix-4 levels use the TT / PP arrays");
+    static_assert(!pw_tight(K) && !pw_pack_tp(K), "the radix-4 levels use the TT / PP arrays");
     const int jA = LK - 1 - jj, jB = jA - 1;
     const int h1 = K >> (jA + 1), h2 = 2 * h1;
     const int role = ((t & h1) ? 1 : 0) | ((t & h2) ? 2 : 0);
@@ -827,7 +871,7 @@ __device__ __forceinline__ void pw_level4_dif(u64 (&L)[M], int &T, int &S, unsig
 {
     constexpr int K = 1 << LK;
     constexpr unsigned NP = 64 * M, N2 = 2 * NP;
-    static_assert(!pw_tight(K), "the radix-4 levels use the TT / PP arrays");
+    static_assert(!pw_tight(K) && !pw_pack_tp(K), "the radix-4 levels use the TT / PP arrays");
     const int h1 = K >> (jj + 1), h2 = h1 / 2;
     const int role = ((t & h2) ? 1 : 0) | ((t & h1) ? 2 : 0);
     const int t0 = t & ~(h1 | h2);
@@ -1182,7 +1226,7 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
         if (halff) pw_sqrt2<M>(Z, Tz);
         pw_publish<M, LK>(Z, Tz, Sz, Xw, pw_tight(K) ? nullptr : TT, t);
         pw_wave_sync();                                  // own column only
-        pw_combine<M, LK, pw_pd<M, LK>()>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
+        pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
         __syncthreads();                                 // the u64 rows below cross columns
     }
     // signed coefficient c_t = v - s p', v in [0, 2^N'], s = (v > 2^(N'-1))
@@ -1310,8 +1354,8 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
     const int t = threadIdx.x;
     u64 *X = (u64 *)smem;                        // M K limbs (2M word rows during the transforms)
     u32 *Xw = (u32 *)smem;
-    int *TT = pw_tight(K) ? nullptr : (int *)(X + (size_t)M * K);    // K (none in the tight form)
-    unsigned *PP = pw_tight(K) ? nullptr : (unsigned *)(TT + K);     // K
+    int *TT = pw_tight(K) ? nullptr : (int *)(Xw + pw_row_words(M, K));    // K (none in the tight form), after the exchange rows
+    unsigned *PP = pw_tight(K) || pw_pack_tp(K) ? nullptr : (unsigned *)(TT + K);     // K (none where the tops carry them: pw_pack_tp)
     int *H = (int *)smem;                        // l, over X (pw_slot_output)
     const int cbw = cb_words(l);
     constexpr int CLP = pw_piece_limbs<M, LK>();   // == l / K (host: pw_inner_limbs)
@@ -1521,7 +1565,7 @@ __device__ __forceinline__ void pw_slot_square(u64 (&La)[M], int Ta, u64 *X, u32
         if (halff) pw_sqrt2<M>(Z, Tz);
         pw_publish<M, LK>(Z, Tz, Sz, Xw, pw_tight(K) ? nullptr : TT, t);
         pw_wave_sync();                                  // own column only
-        pw_combine<M, LK, pw_pd<M, LK>()>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
+        pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
         __syncthreads();                                 // the u64 rows below cross columns
     }
     // signed coefficient c_t = v - s p', v in [0, 2^N'], s = (v > 2^(N'-1))
@@ -1561,8 +1605,8 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
     const int t = threadIdx.x;
     u64 *X = (u64 *)smem;
     u32 *Xw = (u32 *)smem;
-    int *TT = pw_tight(K) ? nullptr : (int *)(X + (size_t)M * K);
-    unsigned *PP = pw_tight(K) ? nullptr : (unsigned *)(TT + K);
+    int *TT = pw_tight(K) ? nullptr : (int *)(Xw + pw_row_words(M, K));
+    unsigned *PP = pw_tight(K) || pw_pack_tp(K) ? nullptr : (unsigned *)(TT + K);
     int *H = (int *)smem;
     const int cbw = cb_words(l);
     constexpr int CLP = pw_piece_limbs<M, LK>();
