@@ -1020,12 +1020,10 @@ struct Exec {
         void (*f)(FoldArgs, u64 *, u32 *) = P.fold == 3 ? k_combine_red<3, NT> : k_combine_red<4, NT>;
         // persistent grid: the resident block count (workgroups take tickets until none are left)
         long grid = a.bps;
-        if (FOLD_PERSIST) {
-            int per = 0, ncu = 0, dev = 0;
-            if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess
-                && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)f, NT, 0) == hipSuccess && per > 0 && ncu > 0)
-                grid = std::min<long>(grid, (long)per * ncu);
-        }
+        int per = 0, ncu = 0, dev = 0;
+        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess
+            && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)f, NT, 0) == hipSuccess && per > 0 && ncu > 0)
+            grid = std::min<long>(grid, (long)per * ncu);
         return launch(f, dim3((unsigned)grid), dim3(NT), 0, a, r, st);
     }
 

@@ -279,14 +279,6 @@ __global__ __launch_bounds__(256) void k_cmeta(FoldArgs a)
 // one limb (the limb below a block, for its overflow): every load of it -- KM coefficients'
 // window words and mask words, the A / B terms' meta words -- issued before any is used (a
 // fixed-trip loop of guarded loads, as comb_limb: thread 0 runs this while the block waits)
-// timing probes (A/B builds only, wrong products): bit 0 no limb below the block (fold_limb), bit 1 no
-// carries from the masks, bit 2 no A / B terms
-#ifndef FOLD_PERSIST
-#define FOLD_PERSIST 1   // 0 (A/B builds): one workgroup per ticket, a grid of bps blocks
-#endif
-#ifndef FOLD_PROBE
-#define FOLD_PROBE 0
-#endif
 template <int KM>
 __device__ void fold_limb(const FoldArgs &a, long m, u64 *plo, int *phi)
 {
@@ -460,7 +452,7 @@ __device__ __forceinline__ void fold_thread8(const FoldArgs &a, long mW, long mA
             const u32 vm = (lb >= 8 || ub <= 0) ? 0u : ((ub >= 8 ? 0xffu : (1u << ub) - 1u) & ~((1u << lb) - 1u));
             cb = ((u32)pbits & vm) | (((u32)nbits & vm) << 8);
         }
-        if ((FOLD_PROBE & 2) == 0 && __ballot(cb != 0)) {   // branch-free per limb: d 2^shc with d in {-1, 0, 1} (shc wave-uniform)
+        if (__ballot(cb != 0)) {   // branch-free per limb: d 2^shc with d in {-1, 0, 1} (shc wave-uniform)
             const int shc = (64 - r) & 63;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -524,7 +516,7 @@ __global__ __launch_bounds__(NT, KM <= 3 ? 2048 / NT : 1) void k_combine_red(Fol
     const long nb = a.bps;   // st[nb]: the ticket counter
     if (threadIdx.x == 0) sh_b = __hip_atomic_fetch_add(&st[nb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    // persistent (FOLD_PERSIST: a grid of about the resident block count): a workgroup takes tickets
+    // persistent (a grid of about the resident block count): a workgroup takes tickets
     // until they run out, the next one requested at the start of this one's work so its round trip
     // hides under the loads; each ticket's work is the one-block body below
     for (;;) {
@@ -550,7 +542,7 @@ __global__ __launch_bounds__(NT, KM <= 3 ? 2048 / NT : 1) void k_combine_red(Fol
         if (t == 0) {
             u64 l0 = 0;
             int h0 = 0;
-            if ((FOLD_PROBE & 1) == 0 && base > 0 && base < total) fold_limb<KM>(a, base - 1, &l0, &h0);
+            if (base > 0 && base < total) fold_limb<KM>(a, base - 1, &l0, &h0);
             H[0] = h0;
         }
         __syncthreads();

@@ -37,34 +37,21 @@
 // complements of rows 0 .. 2, pw_group) + one K-word array of tops and pending exponents
 // (pw_pack_tp).  C3 (M = 18, K = 256): 40 960 B, exactly a quarter of a CU's 160 KiB, so four
 // workgroups share it (pw_wpe).
-// Tight form (PW_TIGHT9, K = 512): no top / pending-exponent arrays beside the exchange rows --
+// Tight form (K = 512): no top / pending-exponent arrays beside the exchange rows --
 // a level's partner tops and exponents go by a wave shuffle (partner in the wave) or through
 // the first two exchange rows before the words are published (two more barriers), and the
 // signed coefficients are stored as two's complement (no sign array) -- so the workgroup needs
-// exactly M K 8 bytes: 80 KiB at C4 (M = 20), two workgroups per CU instead of one.
-#ifndef PW_TIGHT9
-#define PW_TIGHT9 1   // 0: the round-3 form (86 KB, one workgroup per CU at C4), for A/B builds
-#endif
-__host__ __device__ constexpr bool pw_tight(int K) { return PW_TIGHT9 && K == 512; }
+// exactly M K 8 bytes: 80 KiB at C4 (M = 20), two workgroups per CU instead of one (the round-3
+// form took 86 KB, one workgroup per CU).
+__host__ __device__ constexpr bool pw_tight(int K) { return K == 512; }
 // operand B's pieces loaded after A's forward transform (pw_slot_product's loadB): the tight
 // form only (C4 pointwise 39.0 -> 37.7 ms; at l = 2048, four workgroups per CU, 0.5-2 % slower:
 // profiles/r04/pw_tight_ab.txt)
-#ifndef PW_LATE_B_ALL
-#define PW_LATE_B_ALL 0   // A/B builds: the late operand-B load at every size
-#endif
-__host__ __device__ constexpr bool pw_late_b(int K) { return pw_tight(K) || PW_LATE_B_ALL; }
+__host__ __device__ constexpr bool pw_late_b(int K) { return pw_tight(K); }
 // inputs in flight in the late operand-B quad loader: one (A's transformed limbs are live; with two
 // the C4 kernel spilled 40 B per lane, with one it has no scratch at all, at equal speed:
-// C4 pointwise 32.41 vs 32.49 ms, profiles/r05/pw_late_infl_ab.txt).  A/B builds: -DPW_LATE_INFL=2
-#ifndef PW_LATE_INFL
-#define PW_LATE_INFL 1
-#endif
-#ifndef PW_A_INFL
-#define PW_A_INFL 2       // A/B builds: inputs in flight in operand A's quad loader (1, 2 or 4)
-#endif
-#ifndef PW_QUAD4
-#define PW_QUAD4 0        // A/B builds: the quad loader's four inputs in flight at once
-#endif
+// C4 pointwise 32.41 vs 32.49 ms, profiles/r05/pw_late_infl_ab.txt); in operand A's: two
+constexpr int pw_late_infl = 1, pw_a_infl = 2;
 
 // Grouped wrap selects (pw_combine GRP): the exchange has GRP - 1 rows more, rows 2M .. 2M+GRP-2
 // = ~rows 0 .. GRP-2, so a reader takes the wrap test, the base select and the mask select once
@@ -73,22 +60,22 @@ __host__ __device__ constexpr bool pw_late_b(int K) { return pw_tight(K) || PW_L
 // fits four workgroups per CU only with the tops and pending exponents packed into one K-word
 // array (pw_pack_tp).  C3, ms per multiply: 7.13-7.16 per word, 6.85-6.90 in pairs, 6.78-6.80 in
 // fours (profiles/r12/pw_pair_ab.txt).
-#ifndef PW_GROUP
-#define PW_GROUP 4        // A/B builds: 1 the per-word form, rows [0, 2M) only; 2 pairs, one row more
-#endif
-static_assert(PW_GROUP == 1 || PW_GROUP == 2 || PW_GROUP == 4, "group sizes built");
-__host__ __device__ constexpr int pw_group(int K) { return pw_tight(K) ? 1 : PW_GROUP; }
+__host__ __device__ constexpr int pw_group(int K) { return pw_tight(K) ? 1 : 4; }
 // tops and pending exponents in one word per thread, (2 T + S) << 12 | P  (P < 2 N' < 2^12; the
 // tops are a few units: pw_norm, pw_sqrt2)
-__host__ __device__ constexpr bool pw_pack_tp(int K) { return pw_group(K) == 4; }
-// 32-bit words of the exchange rows ahead of the tops (TT) and pending exponents (PP)
+__host__ __device__ constexpr bool pw_pack_tp(int K) { return !pw_tight(K); }
+// 32-bit words of the exchange rows ahead of the packed tops and pending exponents (TT)
 __host__ __device__ constexpr size_t pw_row_words(int M, int K) { return (size_t)(2 * M + pw_group(K) - 1) * K; }
 
 __host__ __device__ constexpr size_t pw_lds_bytes(int M, int K, int l)
 {
     return (pw_row_words(M, K) * 4 > (size_t)l * 4 ? pw_row_words(M, K) * 4 : (size_t)l * 4) +
-           (pw_tight(K) ? 0 : pw_pack_tp(K) ? (size_t)K * 4 : (size_t)K * 8);
+           (pw_pack_tp(K) ? (size_t)K * 4 : 0);
 }
+// the shipped shapes (pw_wpe): a quarter of a CU's 160 KiB at C3, half at C4
+static_assert(pw_lds_bytes(10, 256, 1024) == 24576, "M = 10, K = 256, l = 1024");
+static_assert(pw_lds_bytes(18, 256, 2048) == 40960, "M = 18, K = 256, l = 2048");
+static_assert(pw_lds_bytes(20, 512, 4096) == 81920, "M = 20, K = 512, l = 4096");
 
 // waves per SIMD k_pwss is compiled for: 4 (VGPRs <= 128) where the LDS fits 1024 threads per
 // CU (K = 256: four workgroups; the tight K = 512 form: two), else 2 (the compiler's choice,
@@ -99,14 +86,8 @@ __host__ __device__ constexpr int pw_wpe()
     return pw_lds_bytes(M, 1 << LK, 64 * M) * (1024 >> LK) <= 160 * 1024 ? 4 : 2;
 }
 // partner-word prefetch distance of pw_combine for that budget
-#ifndef PW_PD_TIGHT
-#define PW_PD_TIGHT 16
-#endif
 template <int M, int LK>
-#ifndef PW_PD_WIDE
-#define PW_PD_WIDE 16     // A/B builds: the same for the K = 256 kernels
-#endif
-__host__ __device__ constexpr int pw_pd() { return pw_wpe<M, LK>() == 4 ? (pw_tight(1 << LK) ? PW_PD_TIGHT : PW_PD_WIDE) : 2 * M; }
+__host__ __device__ constexpr int pw_pd() { return pw_wpe<M, LK>() == 4 ? 16 : 2 * M; }
 
 // Exchange format: thread t publishes its value as 2M 32-bit words, word k at
 // Xw[k K + t] (conflict-free for any rotation), top in TT[t]; where pw_group(K) = G > 1, also the
@@ -605,8 +586,8 @@ __host__ __device__ __forceinline__ void pw_mulmod(ZT &&Z, int &T, const u64 (&L
     T = -(int)bw;   // value = Z + T 2^N', T in {-1, 0}
 }
 
-// exchange: thread t publishes its value as words (normalised first: pw_norm) and, unless
-// TT is null (tight form), its top
+// exchange: thread t publishes its value as words (normalised first: pw_norm); its top and
+// pending exponent are the caller's (pw_level)
 template <int M, int LK>
 __device__ __forceinline__ void pw_publish_words(const u64 (&L)[M], u32 *Xw, int t)
 {
@@ -626,14 +607,6 @@ __device__ __forceinline__ void pw_publish_words(const u64 (&L)[M], u32 *Xw, int
         col[(2 * M + 1) * K] = ~(u32)(L[0] >> 32);
         col[(2 * M + 2) * K] = ~(u32)L[1];
     }
-}
-
-template <int M, int LK>
-__device__ __forceinline__ void pw_publish(u64 (&L)[M], int &T, int S, u32 *Xw, int *TT, int t)
-{
-    T = pw_norm<M>(L, T);
-    pw_publish_words<M, LK>(L, Xw, t);
-    if (TT) TT[t] = 2 * T + S;
 }
 
 // One forward (DIF) or inverse (DIT) length-K cyclic transform with root 2^W2 over
@@ -689,12 +662,6 @@ __device__ __forceinline__ void pw_combine_fixed(u64 (&L)[M], int &T, int &S, in
     }
 }
 
-#ifndef PW_UNW_FUSE
-#define PW_UNW_FUSE 1   // 0 (A/B builds): the un-weighting as its own publish + rotated read after the inverse
-#endif
-#ifndef PW_PROBE_NOH1
-#define PW_PROBE_NOH1 0   // 1: timing probe, the h = 1 levels without their LDS round (A/B builds only)
-#endif
 // one level jj of the transform.  FIXJ >= 0 (forward transforms, level jj = FIXJ): E mod N' is
 // wave-uniform and one of 2^FIXJ compile-time values (level 0: exactly N'/2) -- pw_transform
 // UNW (the inverse's last level, h = K/2): the un-weighting theta^-t 2^-lk folded in -- with F the
@@ -713,8 +680,8 @@ __device__ __forceinline__ unsigned pw_unweight_exp(unsigned Pz, unsigned W2, in
 }
 
 template <int M, int LK, int DIR, int FIXJ, bool UNW = false>
-__device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &P, u32 *Xw, int *TT, unsigned *PP,
-                                         unsigned W2, int t, int jj, bool unw = false)
+__device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &P, u32 *Xw, int *TT, unsigned W2, int t,
+                                         int jj, bool unw = false)
 {
     constexpr int K = 1 << LK, lk = LK;
     constexpr unsigned N2 = 128 * M;
@@ -726,19 +693,6 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
     // (qt mod h) 2^j < K/2, times W2: below N' (= K W2 / 2): no reduction needed
     const unsigned tw = (unsigned)((qt & (h - 1)) << j) * W2;
     const bool cross = h >= 64;                  // partner in another wave
-#if PW_PROBE_NOH1
-    if (h == 1) {   // timing probe (A/B builds only, wrong products): the h = 1 level without its LDS round
-        u64 cy = P;
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-            const u64 s = L[m] + cy;
-            cy = s < L[m] ? 1 : 0;
-            L[m] = s;
-        }
-        if (!top) P = pw_mod(P + 1, N2);
-        return;
-    }
-#endif
     unsigned Pq;
     int packed;
     if (pw_tight(K)) {
@@ -760,22 +714,16 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
         pw_publish_words<M, LK>(L, Xw, t);
         if (cross) __syncthreads(); else pw_wave_sync();
     } else {
-        if constexpr (pw_pack_tp(K)) {
-            pw_publish<M, LK>(L, T, S, Xw, nullptr, t);
-            TT[t] = (int)((unsigned)(2 * T + S) << 12 | P);
-            if (cross) __syncthreads(); else pw_wave_sync();
-            const int tp = TT[q];
-            Pq = (unsigned)tp & 4095u;
-            packed = tp >> 12;
-        } else {
-            pw_publish<M, LK>(L, T, S, Xw, TT, t);
-            PP[t] = P;
-            if (cross) __syncthreads(); else pw_wave_sync();
-            Pq = PP[q];
-            packed = TT[q];
-        }
+        // top / sign and pending exponent in one word (pw_pack_tp)
+        T = pw_norm<M>(L, T);
+        pw_publish_words<M, LK>(L, Xw, t);
+        TT[t] = (int)((unsigned)(2 * T + S) << 12 | P);
+        if (cross) __syncthreads(); else pw_wave_sync();
+        const int tp = TT[q];
+        Pq = (unsigned)tp & 4095u;
+        packed = tp >> 12;
     }
-    const int own_packed = 2 * T + S;   // (UNW) as published: T normalised by pw_publish / pw_norm
+    const int own_packed = 2 * T + S;   // (UNW) as published: T normalised by pw_norm
     unsigned E;
     if (DIR == 0) {
         // top: X_t + X_q = 2^P (x_t + 2^(Pq-P) x_q); bottom: (X_q - X_t) w^tw = 2^(P+tw) (2^(Pq-P) x_q - x_t)
@@ -812,107 +760,13 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
     if (cross) __syncthreads(); else pw_wave_sync();
 }
 
-// Two DIT levels per exchange (A/B builds: -DPW_R4_INV=1): levels jj (pairs h1 =
-// K >> (lk - jj)) and jj + 1 (h2 = 2 h1) on the quad t0 | {0, h1, h2, h1 + h2} of role i = [t & h1]
-// + 2 [t & h2], from one publish: with A, B_i the two levels' twiddles (B_i that of the level-(jj+1)
-// pair holding t) every output is v_i = sum_r sigma_ir w^-e_ir Z_r, e_i0 = 0, e_i1 = A, e_i2 = B_i,
-// e_i3 = A + B_i, sigma_i1 = -[i odd], sigma_i2 = -[i >= 2], sigma_i3 = sigma_i1 sigma_i2 -- own term
-// plus three rotated partner reads (pw_combine), one barrier pair instead of two.  Same LDS traffic
-// (one 2M-word publish + three reads against two + two), 1.5x the add chains.
-#ifndef PW_R4_INV
-#define PW_R4_INV 0
-#endif
-template <int M, int LK>
-__device__ __forceinline__ void pw_level4_dit(u64 (&L)[M], int &T, int &S, unsigned &P, u32 *Xw, int *TT, unsigned *PP,
-                                              unsigned W2, int t, int jj)
-{
-    constexpr int K = 1 << LK;
-    constexpr unsigned NP = 64 * M, N2 = 2 * NP;
-    static_assert(!pw_tight(K) && !pw_pack_tp(K), "the radix-4 levels use the TT / PP arrays");
-    const int jA = LK - 1 - jj, jB = jA - 1;
-    const int h1 = K >> (jA + 1), h2 = 2 * h1;
-    const int role = ((t & h1) ? 1 : 0) | ((t & h2) ? 2 : 0);
-    const int t0 = t & ~(h1 | h2);
-    const unsigned A = (unsigned)((t & (h1 - 1)) << jA) * W2;   // < N' (as pw_level's tw)
-    const unsigned B = (unsigned)((t & (h2 - 1)) << jB) * W2;
-    const bool cross = h2 >= 64;
-    pw_publish<M, LK>(L, T, S, Xw, TT, t);
-    PP[t] = P;
-    if (cross) __syncthreads(); else pw_wave_sync();
-    const unsigned eA = A ? N2 - A : 0u, eB = B ? N2 - B : 0u;
-    auto ex = [&](int r) -> unsigned { return r == 0 ? 0u : r == 1 ? eA : r == 2 ? eB : pw_mod(eA + eB, N2); };
-    const bool n1 = role & 1, n2 = (role >> 1) & 1;
-    auto neg = [&](int r) -> bool { return r == 0 ? false : r == 1 ? n1 : r == 2 ? n2 : n1 != n2; };
-    const unsigned Pn = pw_mod(P + ex(role), N2);
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        const int r = role ^ k;
-        const int q = t0 | ((r & 1) ? h1 : 0) | ((r & 2) ? h2 : 0);
-        const unsigned Pq = PP[q];
-        const int packed = TT[q];
-        unsigned E = pw_mod(Pq + ex(r) + 2 * N2 - Pn, N2);
-        if (neg(r)) E = pw_mod(E + NP, N2);
-        pw_combine<M, LK, pw_pd<M, LK>()>(L, T, S, k == 1 ? (neg(role) ? -1 : 1) : 1, Xw, packed, q, E);
-    }
-    P = Pn;
-    if (cross) __syncthreads(); else pw_wave_sync();
-}
-
-// The same for two DIF levels (A/B builds: -DPW_R4_FWD=1): levels jj (h1 = K >> (jj + 1)) and
-// jj + 1 (h2 = h1 / 2), role i = [t & h2] + 2 [t & h1]; with a_r = ((t0 | [r odd] h2) mod h1) 2^jj W2
-// and B = (t0 mod h2) 2^(jj+1) W2, v_i = sum_r (-1)^popcount(i & r) w^e_ir X_r,
-// e_ir = [i odd] B + [i >= 2] a_r.
-#ifndef PW_R4_FWD
-#define PW_R4_FWD 0
-#endif
-template <int M, int LK>
-__device__ __forceinline__ void pw_level4_dif(u64 (&L)[M], int &T, int &S, unsigned &P, u32 *Xw, int *TT, unsigned *PP,
-                                              unsigned W2, int t, int jj)
-{
-    constexpr int K = 1 << LK;
-    constexpr unsigned NP = 64 * M, N2 = 2 * NP;
-    static_assert(!pw_tight(K) && !pw_pack_tp(K), "the radix-4 levels use the TT / PP arrays");
-    const int h1 = K >> (jj + 1), h2 = h1 / 2;
-    const int role = ((t & h2) ? 1 : 0) | ((t & h1) ? 2 : 0);
-    const int t0 = t & ~(h1 | h2);
-    const unsigned a0 = (unsigned)((t0 & (h1 - 1)) << jj) * W2, a1 = (unsigned)(((t0 | h2) & (h1 - 1)) << jj) * W2;
-    const unsigned B = (unsigned)((t0 & (h2 - 1)) << (jj + 1)) * W2;
-    const bool cross = h1 >= 64;
-    pw_publish<M, LK>(L, T, S, Xw, TT, t);
-    PP[t] = P;
-    if (cross) __syncthreads(); else pw_wave_sync();
-    auto ex = [&](int i, int r) -> unsigned {
-        return pw_mod(((i & 1) ? B : 0u) + ((i & 2) ? ((r & 1) ? a1 : a0) : 0u), N2);
-    };
-    auto neg = [&](int i, int r) -> bool { return __builtin_popcount(i & r) & 1; };
-    const unsigned Pn = pw_mod(P + ex(role, role), N2);
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        const int r = role ^ k;
-        const int q = t0 | ((r & 1) ? h2 : 0) | ((r & 2) ? h1 : 0);
-        const unsigned Pq = PP[q];
-        const int packed = TT[q];
-        unsigned E = pw_mod(Pq + ex(role, r) + 2 * N2 - Pn, N2);
-        if (neg(role, r)) E = pw_mod(E + NP, N2);
-        pw_combine<M, LK, pw_pd<M, LK>()>(L, T, S, k == 1 ? (neg(role, role) ? -1 : 1) : 1, Xw, packed, q, E);
-    }
-    P = Pn;
-    if (cross) __syncthreads(); else pw_wave_sync();
-}
-
 // the highest compile-time-rotation level of operand B's transform in the late-B (l = 4096) form:
 // level 0 only -- while B transforms, A's transformed limbs are live, and the switch copies of
 // levels 1 and 2 pushed the kernel into spilling (96 -> 40 B per lane; C4 pointwise 34.0 -> 32.3 ms,
-// levels 0-1: 32.6; profiles/r05/pw_fixb_ab.txt).  A/B builds: -DPW_FIXB=1 / 2
-#ifndef PW_FIXB
-#define PW_FIXB 0
-#endif
-#ifndef PW_FIXB_EARLY
-#define PW_FIXB_EARLY 2   // A/B builds: the same for operand B loaded with A (l <= 2048)
-#endif
+// levels 0-1: 32.6; profiles/r05/pw_fixb_ab.txt); operand B loaded with A (l <= 2048): levels 0-2
+constexpr int pw_fixb_late = 0, pw_fixb_early = 2;
 template <int M, int LK, int DIR, int FIXMAX = 2>
-__device__ __forceinline__ void pw_transform(u64 (&L)[M], int &T, int &S, unsigned &P, u32 *Xw, int *TT, unsigned *PP,
-                                             unsigned W2, int t)
+__device__ __forceinline__ void pw_transform(u64 (&L)[M], int &T, int &S, unsigned &P, u32 *Xw, int *TT, unsigned W2, int t)
 {
     int jj = 0;
     if (DIR == 0) {
@@ -928,18 +782,12 @@ __device__ __forceinline__ void pw_transform(u64 (&L)[M], int &T, int &S, unsign
         // per-word wrap tests, addresses and complement masks fold away).  Each level is its own
         // inlined copy (peeled off the loop: one loop body with both forms spilled 3x more).
         static_assert(LK >= 7, "level 0's partner K/2 >= 64 lanes away");
-        pw_level<M, LK, DIR, 0>(L, T, S, P, Xw, TT, PP, W2, t, 0);
-        if constexpr (LK >= 8 && FIXMAX >= 1) pw_level<M, LK, DIR, 1>(L, T, S, P, Xw, TT, PP, W2, t, 1);   // h = K/4 >= 64
-        if constexpr (LK >= 9 && FIXMAX >= 2) pw_level<M, LK, DIR, 2>(L, T, S, P, Xw, TT, PP, W2, t, 2);   // h = K/8 >= 64
+        pw_level<M, LK, DIR, 0>(L, T, S, P, Xw, TT, W2, t, 0);
+        if constexpr (LK >= 8 && FIXMAX >= 1) pw_level<M, LK, DIR, 1>(L, T, S, P, Xw, TT, W2, t, 1);   // h = K/4 >= 64
+        if constexpr (LK >= 9 && FIXMAX >= 2) pw_level<M, LK, DIR, 2>(L, T, S, P, Xw, TT, W2, t, 2);   // h = K/8 >= 64
         jj = LK >= 9 && FIXMAX >= 2 ? 3 : LK >= 8 && FIXMAX >= 1 ? 2 : 1;
     }
-    if constexpr (DIR == 1 && PW_R4_INV && !pw_tight(1 << LK)) {
-        for (; jj + 1 < LK; jj += 2) pw_level4_dit<M, LK>(L, T, S, P, Xw, TT, PP, W2, t, jj);
-    }
-    if constexpr (DIR == 0 && PW_R4_FWD && !pw_tight(1 << LK)) {
-        for (; jj + 1 < LK; jj += 2) pw_level4_dif<M, LK>(L, T, S, P, Xw, TT, PP, W2, t, jj);
-    }
-    for (; jj < LK; ++jj) pw_level<M, LK, DIR, -1, DIR == 1 && PW_UNW_FUSE>(L, T, S, P, Xw, TT, PP, W2, t, jj, jj == LK - 1);
+    for (; jj < LK; ++jj) pw_level<M, LK, DIR, -1, DIR == 1>(L, T, S, P, Xw, TT, W2, t, jj, jj == LK - 1);
 }
 
 // Piece t of a coefficient in the reduced HBM form (coeff.hpp: limbs + carry masks +
@@ -985,14 +833,7 @@ __device__ __forceinline__ void pw_piece_fetch(PwRaw<LP> &R, const u64 *dig, con
     R.top = *topp;
 }
 
-// Piece t of a coefficient in the reduced HBM form (coeff.hpp: limbs + carry masks +
-// carry limb): limbs [t LP, t LP + LP) plus the carries into them -- the carry out of
-// limb m lands in limb m + 1, the carry into limb 0 is minus the carry out of limb l-1
-// and minus the carry limb (both weigh 2^N == -1); the carry out of the piece's top limb
-// is the next piece's.  The value v (-2 <= v < 2^(64 LP) + 2^(64 LP - 64)) is returned as
-// L + T 2^N', T in {-1, 0}: the convolution tolerates such pieces (|c_t| < K 2^(2B+1)
-// still fits the headroom N' >= 2B + lk + 4, pdispatch.hpp), so the pointwise inputs need no
-// canonicalisation pass.  A piece lies inside one 64-limb mask row (LP | 64).
+// the piece's value from its loaded bytes (above)
 template <int M, int LP>
 __device__ __forceinline__ void pw_piece_make(u64 (&L)[M], int &T, const PwRaw<LP> &R, int l, int t)
 {
@@ -1104,18 +945,7 @@ __device__ __forceinline__ void pw_load_quad_bfly(u64 (&L)[M], int &T, const u64
             acc[j] = ((u64)hi << 32) | lo;
         }
     };
-    if (PW_QUAD4 || INFL == 4) {   // all four inputs' bytes in flight at once
-        const int pr = pos >= 2 ? tr : t;
-        PwRaw<LP> R0, R1, R2, R3;
-        pw_piece_fetch<LP>(R0, dig + (size_t)s0 * l, cb + (size_t)s0 * cbw, top + s0, l, t);
-        pw_piece_fetch<LP>(R2, dig + (size_t)(s0 + 2) * l, cb + (size_t)(s0 + 2) * cbw, top + s0 + 2, l, t);
-        pw_piece_fetch<LP>(R1, dig + (size_t)(s0 + 1) * l, cb + (size_t)(s0 + 1) * cbw, top + s0 + 1, l, pr);
-        pw_piece_fetch<LP>(R3, dig + (size_t)(s0 + 3) * l, cb + (size_t)(s0 + 3) * cbw, top + s0 + 3, l, pr);
-        add(R0, 0, t);
-        add(R2, 2, t);
-        add(R1, 1, pr);
-        add(R3, 3, pr);
-    } else if (INFL == 1) {   // one input's bytes at a time (x0, x2, x1, x3)
+    if (INFL == 1) {   // one input's bytes at a time (x0, x2, x1, x3)
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int q = u < 2 ? 2 * u : 2 * (u - 2) + 1, pt = (q & 1) && pos >= 2 ? tr : t;
@@ -1141,6 +971,67 @@ __device__ __forceinline__ void pw_load_quad_bfly(u64 (&L)[M], int &T, const u64
     T = (i64)acc[LP] < 0 ? -1 : 0;
 }
 
+// diagnostics (MPFFT_PW_STAMPS): thread 0 stamps phase boundary k of this workgroup
+__device__ __forceinline__ void pw_stamp(unsigned long long *stamp, int t, int k)
+{
+    if (stamp && t == 0) stamp[k] = __builtin_amdgcn_s_memtime();
+}
+
+// omega = 2^W2, W2 = 2 N' / K (host: K / 2 divides N')
+template <int M, int LK>
+__host__ __device__ constexpr unsigned pw_w2()
+{
+    static_assert(((128u * M) >> LK) << LK == 128u * M, "omega must be a power of two");
+    return (128u * M) >> LK;
+}
+
+// exponent of the negacyclic weight theta^t = 2^(t W2 / 2); a half-integer exponent (W2 and t odd)
+// is 2^(floor(t W2 / 2) + N'/4) (2^(N'/2) - 1)  (sqrt 2 = 2^(N'/4) (2^(N'/2) - 1) in R'), the
+// (2^(N'/2) - 1) by the caller (pw_sqrt2)
+template <int M, int LK>
+__device__ __forceinline__ unsigned pw_weight_exp(int t)
+{
+    constexpr unsigned NP = 64 * M, W2 = pw_w2<M, LK>();
+    return (((unsigned)t * W2) >> 1) + (((W2 & 1) && (t & 1)) ? NP / 4 : 0);   // < N' + N'/4
+}
+
+// The end of a slot's inner product or square, from the pointwise results 2^Pz (-1)^Sz (Z, Tz): the
+// inverse transform with 2^-lk (division by K) and theta^-t, then the signed coefficients c_t into
+// X (limb-major, M rows) and their signs (+ limb M) into TT; stamps 5 and 6, ends with a barrier
+template <int M, int LK>
+__device__ __forceinline__ void pw_slot_tail(u64 (&Z)[M], int Tz, int Sz, unsigned Pz, u64 *X, u32 *Xw, int *TT, int t,
+                                             unsigned long long *stamp)
+{
+    constexpr int K = 1 << LK;
+    constexpr unsigned W2 = pw_w2<M, LK>();
+    pw_transform<M, LK, 1>(Z, Tz, Sz, Pz, Xw, TT, W2, t);
+    pw_stamp(stamp, t, 5);
+    // the rotation by theta^-t 2^-lk rode in the last level (pw_level UNW); the (2^(N'/2) - 1)
+    // of a half-integer weight commutes with it (that level ended with a barrier: the u64 rows
+    // below may cross columns)
+    const int tf = pw_tight(K) ? pw_launder(t) : t;
+    if ((W2 & 1) && (tf & 1)) pw_sqrt2<M>(Z, Tz);
+    // signed coefficient c_t = v - s p', v in [0, 2^N'], s = (v > 2^(N'-1))
+    const int zt = pw_canon<M>(Z, Tz);
+    const int neg = zt || (Z[M - 1] >> 63);
+    if (pw_tight(K)) {
+        // as N'-bit two's complement: v - s (v - 1 = 2^N' - 1 for v = 2^N'), its top bit the sign
+        u64 b = (u64)neg;
+#pragma unroll
+        for (int j = 0; j < M; ++j) {
+            const u64 z = Z[j];
+            X[j * K + t] = z - b;
+            b = b && z == 0;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < M; ++j) X[j * K + t] = Z[j];
+        TT[t] = neg | (zt << 1);                     // s, and limb M of v (2^N' only)
+    }
+    __syncthreads();
+    pw_stamp(stamp, t, 6);
+}
+
 // inner product of one slot: forward transforms of the pieces (La, Ta), (Lb, Tb), the
 // pointwise products in R', the inverse and the un-weighting; leaves the signed
 // coefficients c_t in X (limb-major, M rows) and their signs (+ limb M) in TT (ends with a barrier)
@@ -1149,40 +1040,32 @@ __device__ __forceinline__ void pw_load_quad_bfly(u64 (&L)[M], int &T, const u64
 // kernel's register peak at 128 VGPRs; B's load latency is hidden by the CU's other workgroup)
 template <int M, int LK, typename LoadB = int>
 __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[M], int Tb, u64 *X, u32 *Xw, int *TT,
-                                                unsigned *PP, int t, unsigned long long *stamp, LoadB loadB = 0)
+                                                int t, unsigned long long *stamp, LoadB loadB = 0)
 {
     constexpr bool late_b = !std::is_same<LoadB, int>::value;
-#define PW_STAMP(k) do { if (stamp && t == 0) stamp[k] = __builtin_amdgcn_s_memtime(); } while (0)
-    constexpr int K = 1 << LK, lk = LK;
-    constexpr unsigned NP = 64 * M, N2 = 2 * NP;
-    constexpr unsigned W2 = N2 >> lk;            // omega = 2^W2 (host: K / 2 divides N')
-    static_assert((N2 >> lk) << lk == N2, "omega must be a power of two");
+    constexpr int K = 1 << LK;
+    constexpr unsigned N2 = 128 * M, W2 = pw_w2<M, LK>();
     int Sa = 0, Sb = 0;                          // sign flags
-    // negacyclic weight theta^t = 2^(t W2 / 2); a half-integer exponent (W2 and t odd) is
-    // 2^(floor(t W2 / 2) + N'/4) (2^(N'/2) - 1)  (sqrt 2 = 2^(N'/4) (2^(N'/2) - 1) in R').
-    // Recomputed from an opaque copy of t where used again at l = 4096 (pw_launder): kept live
-    // from here to the un-weighting they took VGPRs that kernel spilled (144 -> 96 B per lane,
-    // C4 pointwise 35.8 -> 34.9 ms)
-    auto weight = [&](int tt) -> unsigned {
-        return (((unsigned)tt * W2) >> 1) + (((W2 & 1) && (tt & 1)) ? NP / 4 : 0);   // < N' + N'/4
-    };
+    // negacyclic weight theta^t (pw_weight_exp).  Recomputed from an opaque copy of t where used
+    // again at l = 4096 (pw_launder): kept live from here to the un-weighting they took VGPRs that
+    // kernel spilled (144 -> 96 B per lane, C4 pointwise 35.8 -> 34.9 ms)
     const bool half = (W2 & 1) && (t & 1);
-    unsigned Pa = weight(t), Pb = late_b ? 0u : Pa;
+    unsigned Pa = pw_weight_exp<M, LK>(t), Pb = late_b ? 0u : Pa;
     if (half) {
         pw_sqrt2<M>(La, Ta);
         if (!late_b) pw_sqrt2<M>(Lb, Tb);
     }
-    PW_STAMP(1);
-    pw_transform<M, LK, 0>(La, Ta, Sa, Pa, Xw, TT, PP, W2, t);
-    PW_STAMP(2);
+    pw_stamp(stamp, t, 1);
+    pw_transform<M, LK, 0>(La, Ta, Sa, Pa, Xw, TT, W2, t);
+    pw_stamp(stamp, t, 2);
     if constexpr (late_b) {
         loadB(Lb, Tb);
         const int tb = pw_launder(t);
-        Pb = weight(tb);
+        Pb = pw_weight_exp<M, LK>(tb);
         if ((W2 & 1) && (tb & 1)) pw_sqrt2<M>(Lb, Tb);
     }
-    pw_transform<M, LK, 0, late_b ? PW_FIXB : PW_FIXB_EARLY>(Lb, Tb, Sb, Pb, Xw, TT, PP, W2, t);
-    PW_STAMP(3);
+    pw_transform<M, LK, 0, late_b ? pw_fixb_late : pw_fixb_early>(Lb, Tb, Sb, Pb, Xw, TT, W2, t);
+    pw_stamp(stamp, t, 3);
 
     // ---- inner products: 2^Pa xa * 2^Pb xb = 2^(Pa + Pb) (xa xb) ---------------------
     const int ca = pw_canon<M>(La, Ta), cb = pw_canon<M>(Lb, Tb);
@@ -1205,50 +1088,9 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
         pw_mulmod<M>(Z, Tz, La, ca, Lb, cb);
     }
     unsigned Pz = pw_mod(Pa + Pb, N2);
-    PW_STAMP(4);
+    pw_stamp(stamp, t, 4);
 
-    // ---- inverse, then 2^-lk (division by K) and theta^-t --------------------------
-    pw_transform<M, LK, 1>(Z, Tz, Sz, Pz, Xw, TT, PP, W2, t);
-    PW_STAMP(5);
-    if constexpr (PW_UNW_FUSE && !(PW_R4_INV && !pw_tight(K) && LK % 2 == 0)) {
-        // the rotation by theta^-t 2^-lk rode in the last level (pw_level UNW); the (2^(N'/2) - 1)
-        // of a half-integer weight commutes with it (that level ended with a barrier: the u64 rows
-        // below may cross columns)
-        const int tf = pw_tight(K) ? pw_launder(t) : t;
-        if ((W2 & 1) && (tf & 1)) pw_sqrt2<M>(Z, Tz);
-    } else {
-        // theta^-t 2^-lk: 2^-(t W2 / 2 + lk), for a half-integer t W2 / 2 (sqrt 2)^-1 = sqrt 2 / 2:
-        // 2^(-floor(t W2 / 2) - 1 - lk + N'/4) (2^(N'/2) - 1)
-        const int tf = pw_tight(K) ? pw_launder(t) : t;   // (at l = 2048 the laundered form measured 1 % slower)
-        const bool halff = (W2 & 1) && (tf & 1);
-        const unsigned un = (((unsigned)tf * W2) >> 1) + lk + (halff ? 1 : 0);   // < N' + lk + 1
-        const unsigned F = pw_mod(Pz + N2 - un + (halff ? NP / 4 : 0), N2);
-        if (halff) pw_sqrt2<M>(Z, Tz);
-        pw_publish<M, LK>(Z, Tz, Sz, Xw, pw_tight(K) ? nullptr : TT, t);
-        pw_wave_sync();                                  // own column only
-        pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
-        __syncthreads();                                 // the u64 rows below cross columns
-    }
-    // signed coefficient c_t = v - s p', v in [0, 2^N'], s = (v > 2^(N'-1))
-    const int zt = pw_canon<M>(Z, Tz);
-    const int neg = zt || (Z[M - 1] >> 63);
-    if (pw_tight(K)) {
-        // as N'-bit two's complement: v - s (v - 1 = 2^N' - 1 for v = 2^N'), its top bit the sign
-        u64 b = (u64)neg;
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-            const u64 z = Z[j];
-            X[j * K + t] = z - b;
-            b = b && z == 0;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < M; ++j) X[j * K + t] = Z[j];
-        TT[t] = neg | (zt << 1);                     // s, and limb M of v (2^N' only)
-    }
-    __syncthreads();
-    PW_STAMP(6);
-#undef PW_STAMP
+    pw_slot_tail<M, LK>(Z, Tz, Sz, Pz, X, Xw, TT, t, stamp);
 }
 
 // R = sum_t c_t 2^(B t) mod 2^N + 1 from X / TT, stored in the reduced HBM form at
@@ -1329,6 +1171,35 @@ __device__ __forceinline__ void pw_slot_output(const u64 *X, const int *TT, int 
     if (t == 0) *topp = 0;
 }
 
+// LDS of a k_pwss / k_pwsq workgroup (pw_lds_bytes)
+struct PwLds {
+    u64 *X;     // M K limbs (2M word rows during the transforms)
+    u32 *Xw;    // the same as words
+    int *TT;    // K (none in the tight form), after the exchange rows
+    int *H;     // l, over X (pw_slot_output)
+};
+template <int M, int LK>
+__device__ __forceinline__ PwLds pw_lds_carve(unsigned char *smem)
+{
+    constexpr int K = 1 << LK;
+    u32 *Xw = (u32 *)smem;
+    return PwLds{(u64 *)smem, Xw, pw_tight(K) ? nullptr : (int *)(Xw + pw_row_words(M, K)), (int *)smem};
+}
+
+// The slot of block b of nb in the fused kernels, XCD-aware: workgroups are dealt round-robin to
+// the 8 XCDs (blockIdx mod 8), each with its own L2.  FUSE 1: blocks b and b + 8 take the two slots
+// of one pair, so the second reads of a pair's four inputs hit the same L2; FUSE 2: blocks b,
+// b + 8, b + 16, b + 24 take the four slots of one quad.  Identity on the tail of < 16 / < 32 blocks.
+template <int FUSE>
+__device__ __forceinline__ long pw_fused_slot(long b, long nb)
+{
+    static_assert(FUSE == 1 || FUSE == 2, "slot pairs or quads");
+    constexpr long G = 1 << FUSE;
+    if (b >= nb - nb % (8 * G)) return b;
+    const long x = b & 7, j = b >> 3;
+    return G * (((j >> FUSE) << 3) + x) + (j & (G - 1));
+}
+
 // k_pwss<M, LK, FUSE>: A[slot] <- A[slot] * B[slot] mod 2^N + 1, one workgroup of K = 2^lk
 // threads per slot; reduced-form inputs and output (HBM format of coeff.hpp).
 // FUSE 1: the inputs are the slot pairs (2i, 2i+1) of a row *before* the last level of the
@@ -1352,11 +1223,7 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int K = 1 << LK;
     const int t = threadIdx.x;
-    u64 *X = (u64 *)smem;                        // M K limbs (2M word rows during the transforms)
-    u32 *Xw = (u32 *)smem;
-    int *TT = pw_tight(K) ? nullptr : (int *)(Xw + pw_row_words(M, K));    // K (none in the tight form), after the exchange rows
-    unsigned *PP = pw_tight(K) || pw_pack_tp(K) ? nullptr : (unsigned *)(TT + K);     // K (none where the tops carry them: pw_pack_tp)
-    int *H = (int *)smem;                        // l, over X (pw_slot_output)
+    const auto [X, Xw, TT, H] = pw_lds_carve<M, LK>(smem);
     const int cbw = cb_words(l);
     constexpr int CLP = pw_piece_limbs<M, LK>();   // == l / K (host: pw_inner_limbs)
     u64 La[M], Lb[M];
@@ -1367,7 +1234,7 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         auto loadB = [&](u64 (&L)[M], int &T) {
             pw_load_piece<M, CLP>(L, T, digB + (size_t)slot * l, cbB + (size_t)slot * cbw, topB + slot, l, t);
         };
-        pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, PP, t, stamp, loadB);
+        pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp, loadB);
         // every piece of A was read before the first barrier of A's transform: the output may
         // overwrite A in place
         pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
@@ -1381,52 +1248,37 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
             pw_piece_make<M, CLP>(Lb, Tb, RB, l, t);
         }
         __syncthreads();   // every piece read before any output limb is written (in place on A)
-        pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, PP, t, stamp);
+        pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp);
         pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
     } else if (FUSE == 2) {
-        // the row DIF's last two levels on load, slot quads: blocks b, b + 8, b + 16, b + 24 take
-        // the four slots of one quad, so they run on one XCD and share its L2 (identity on the
-        // tail of < 32 blocks)
-        const long b = blockIdx.x, nb = gridDim.x, main = nb - nb % 32;
-        long slot = b;
-        if (b < main) {
-            const long x = b & 7, j = b >> 3;
-            slot = 4 * (((j >> 2) << 3) + x) + (j & 3);
-        }
+        // the row DIF's last two levels on load, slot quads
+        const long slot = pw_fused_slot<2>(blockIdx.x, gridDim.x);
         const long s0 = slot & ~3L;
         const int pos = (int)(slot & 3);
-        pw_load_quad_bfly<M, CLP, K, PW_A_INFL>(La, Ta, digA, cbA, topA, s0, pos, l, cbw, t);
+        pw_load_quad_bfly<M, CLP, K, pw_a_infl>(La, Ta, digA, cbA, topA, s0, pos, l, cbw, t);
         if (pw_late_b(K)) {
             // (an opaque copy of t: the piece offsets and mask bit positions of A's loader are not
             // kept live across A's transform for reuse here)
             auto loadB = [&](u64 (&L)[M], int &T) {
-                pw_load_quad_bfly<M, CLP, K, PW_LATE_INFL>(L, T, digB, cbB, topB, s0, pos, l, cbw, pw_launder(t));
+                pw_load_quad_bfly<M, CLP, K, pw_late_infl>(L, T, digB, cbB, topB, s0, pos, l, cbw, pw_launder(t));
             };
-            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, PP, t, stamp, loadB);
+            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp, loadB);
         } else {
             pw_load_quad_bfly<M, CLP, K>(Lb, Tb, digB, cbB, topB, s0, pos, l, cbw, t);
-            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, PP, t, stamp);
+            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp);
         }
         pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
     } else {
-        // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs (blockIdx mod 8), each
-        // with its own L2.  Blocks b and b + 8 take the two slots of one pair, so the second
-        // reads of a pair's four inputs hit the same L2 (identity on the tail of < 16 blocks).
-        const long b = blockIdx.x, nb = gridDim.x, main = nb - nb % 16;
-        long slot = b;
-        if (b < main) {
-            const long x = b & 7, j = b >> 3;
-            slot = 2 * (((j >> 1) << 3) + x) + (j & 1);
-        }
+        const long slot = pw_fused_slot<1>(blockIdx.x, gridDim.x);
         pw_load_pair_bfly<M, CLP>(La, Ta, digA, cbA, topA, slot & ~1L, l, cbw, t, slot & 1);
         if (pw_late_b(K)) {
             auto loadB = [&](u64 (&L)[M], int &T) {
                 pw_load_pair_bfly<M, CLP>(L, T, digB, cbB, topB, slot & ~1L, l, cbw, t, slot & 1);
             };
-            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, PP, t, stamp, loadB);
+            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp, loadB);
         } else {
             pw_load_pair_bfly<M, CLP>(Lb, Tb, digB, cbB, topB, slot & ~1L, l, cbw, t, slot & 1);
-            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, PP, t, stamp);
+            pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp);
         }
         pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
     }
@@ -1516,22 +1368,18 @@ __host__ __device__ __forceinline__ void pw_sqrmod(ZT &&Z, int &T, const u64 (&L
 // leaves the signed coefficients c_t in X and their signs in TT (ends with a barrier).  The
 // stamps keep pw_slot_product's numbering (2 and 3 coincide: there is no second transform).
 template <int M, int LK>
-__device__ __forceinline__ void pw_slot_square(u64 (&La)[M], int Ta, u64 *X, u32 *Xw, int *TT, unsigned *PP, int t,
+__device__ __forceinline__ void pw_slot_square(u64 (&La)[M], int Ta, u64 *X, u32 *Xw, int *TT, int t,
                                                unsigned long long *stamp)
 {
-#define PW_STAMP(k) do { if (stamp && t == 0) stamp[k] = __builtin_amdgcn_s_memtime(); } while (0)
-    constexpr int K = 1 << LK, lk = LK;
-    constexpr unsigned NP = 64 * M, N2 = 2 * NP;
-    constexpr unsigned W2 = N2 >> lk;            // omega = 2^W2 (host: K / 2 divides N')
-    static_assert((N2 >> lk) << lk == N2, "omega must be a power of two");
+    constexpr int K = 1 << LK;
+    constexpr unsigned N2 = 128 * M, W2 = pw_w2<M, LK>();
     int Sa = 0;
-    // negacyclic weight theta^t (pw_slot_product)
-    unsigned Pa = (((unsigned)t * W2) >> 1) + (((W2 & 1) && (t & 1)) ? NP / 4 : 0);   // < N' + N'/4
+    unsigned Pa = pw_weight_exp<M, LK>(t);       // negacyclic weight theta^t
     if ((W2 & 1) && (t & 1)) pw_sqrt2<M>(La, Ta);
-    PW_STAMP(1);
-    pw_transform<M, LK, 0>(La, Ta, Sa, Pa, Xw, TT, PP, W2, t);
-    PW_STAMP(2);
-    PW_STAMP(3);
+    pw_stamp(stamp, t, 1);
+    pw_transform<M, LK, 0>(La, Ta, Sa, Pa, Xw, TT, W2, t);
+    pw_stamp(stamp, t, 2);
+    pw_stamp(stamp, t, 3);
 
     // ---- inner squares: (2^Pa xa)^2 = 2^(2 Pa) xa^2; the sign flag squares away -------
     const int ca = pw_canon<M>(La, Ta);
@@ -1549,44 +1397,9 @@ __device__ __forceinline__ void pw_slot_square(u64 (&La)[M], int Ta, u64 *X, u32
         pw_sqrmod<M>(Z, Tz, La, ca);
     }
     unsigned Pz = pw_mod(2 * Pa, N2);
-    PW_STAMP(4);
+    pw_stamp(stamp, t, 4);
 
-    // ---- inverse, then 2^-lk (division by K) and theta^-t: as pw_slot_product -------
-    pw_transform<M, LK, 1>(Z, Tz, Sz, Pz, Xw, TT, PP, W2, t);
-    PW_STAMP(5);
-    if constexpr (PW_UNW_FUSE && !(PW_R4_INV && !pw_tight(K) && LK % 2 == 0)) {
-        const int tf = pw_tight(K) ? pw_launder(t) : t;
-        if ((W2 & 1) && (tf & 1)) pw_sqrt2<M>(Z, Tz);
-    } else {
-        const int tf = pw_tight(K) ? pw_launder(t) : t;
-        const bool halff = (W2 & 1) && (tf & 1);
-        const unsigned un = (((unsigned)tf * W2) >> 1) + lk + (halff ? 1 : 0);   // < N' + lk + 1
-        const unsigned F = pw_mod(Pz + N2 - un + (halff ? NP / 4 : 0), N2);
-        if (halff) pw_sqrt2<M>(Z, Tz);
-        pw_publish<M, LK>(Z, Tz, Sz, Xw, pw_tight(K) ? nullptr : TT, t);
-        pw_wave_sync();                                  // own column only
-        pw_combine<M, LK, pw_pd<M, LK>(), -1, pw_group(K)>(Z, Tz, Sz, 0, Xw, 2 * Tz + Sz, t, F);   // clears the sign flag
-        __syncthreads();                                 // the u64 rows below cross columns
-    }
-    // signed coefficient c_t = v - s p', v in [0, 2^N'], s = (v > 2^(N'-1))
-    const int zt = pw_canon<M>(Z, Tz);
-    const int neg = zt || (Z[M - 1] >> 63);
-    if (pw_tight(K)) {
-        u64 b = (u64)neg;
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-            const u64 z = Z[j];
-            X[j * K + t] = z - b;
-            b = b && z == 0;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < M; ++j) X[j * K + t] = Z[j];
-        TT[t] = neg | (zt << 1);                     // s, and limb M of v (2^N' only)
-    }
-    __syncthreads();
-    PW_STAMP(6);
-#undef PW_STAMP
+    pw_slot_tail<M, LK>(Z, Tz, Sz, Pz, X, Xw, TT, t, stamp);
 }
 
 // k_pwsq<M, LK, FUSE>: A[slot] <- A[slot]^2 mod 2^N + 1, one workgroup of K = 2^lk threads per
@@ -1603,11 +1416,7 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int K = 1 << LK;
     const int t = threadIdx.x;
-    u64 *X = (u64 *)smem;
-    u32 *Xw = (u32 *)smem;
-    int *TT = pw_tight(K) ? nullptr : (int *)(Xw + pw_row_words(M, K));
-    unsigned *PP = pw_tight(K) || pw_pack_tp(K) ? nullptr : (unsigned *)(TT + K);
-    int *H = (int *)smem;
+    const auto [X, Xw, TT, H] = pw_lds_carve<M, LK>(smem);
     const int cbw = cb_words(l);
     constexpr int CLP = pw_piece_limbs<M, LK>();
     u64 La[M];
@@ -1616,29 +1425,19 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         const long slot = blockIdx.x;
         pw_load_piece<M, CLP>(La, Ta, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
         __syncthreads();   // every piece read before any output limb is written (in place on A)
-        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, PP, t, stamp);
+        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, t, stamp);
         pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
     } else if (FUSE == 2) {
-        const long b = blockIdx.x, nb = gridDim.x, main = nb - nb % 32;
-        long slot = b;
-        if (b < main) {
-            const long x = b & 7, j = b >> 3;
-            slot = 4 * (((j >> 2) << 3) + x) + (j & 3);
-        }
+        const long slot = pw_fused_slot<2>(blockIdx.x, gridDim.x);
         const long s0 = slot & ~3L;
         const int pos = (int)(slot & 3);
-        pw_load_quad_bfly<M, CLP, K, PW_A_INFL>(La, Ta, digA, cbA, topA, s0, pos, l, cbw, t);
-        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, PP, t, stamp);
+        pw_load_quad_bfly<M, CLP, K, pw_a_infl>(La, Ta, digA, cbA, topA, s0, pos, l, cbw, t);
+        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, t, stamp);
         pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
     } else {
-        const long b = blockIdx.x, nb = gridDim.x, main = nb - nb % 16;
-        long slot = b;
-        if (b < main) {
-            const long x = b & 7, j = b >> 3;
-            slot = 2 * (((j >> 1) << 3) + x) + (j & 1);
-        }
+        const long slot = pw_fused_slot<1>(blockIdx.x, gridDim.x);
         pw_load_pair_bfly<M, CLP>(La, Ta, digA, cbA, topA, slot & ~1L, l, cbw, t, slot & 1);
-        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, PP, t, stamp);
+        pw_slot_square<M, LK>(La, Ta, X, Xw, TT, t, stamp);
         pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
     }
     if (stamp) {

@@ -265,24 +265,6 @@ __device__ __forceinline__ Pr rp_get_rot(const RX<PP> &X, int j, int pp, u32 e, 
 // t - 1; thread 0 of round r: thread NT - 1 of round r - 1, round 0: pair HP - 1): those
 // lanes' pairs go through a small LDS table EDGE (NT/64 x G x R x 5 words), one barrier.
 // d = e mod 128 = 32 B + s, workgroup-uniform per slot.
-#ifndef RP_GX_LOAD
-#define RP_GX_LOAD 1   // 0: the round-3 form (plain load, general rotation through LDS), A/B builds only
-#endif
-#ifndef RP_SPLIT_ZSKIP
-#define RP_SPLIT_ZSKIP 1   // 0 (A/B builds): the split pass exchanges its zero slots like any other
-#endif
-#ifndef RP_SPLIT_L0COPY
-#define RP_SPLIT_L0COPY 1  // 0 (A/B builds): the split pass's register level runs its butterflies on zero partners too
-#endif
-#ifndef RP_SPLIT_PUB1
-#define RP_SPLIT_PUB1 1    // 0 (A/B builds): the split pass publishes every live partner slot, copies included
-#endif
-#ifndef RP_SPLIT_LDS
-#define RP_SPLIT_LDS 1    // 0 (A/B builds): the split pass's per-slot guarded loads for whole operands too
-#endif
-#ifndef RP_SPLIT_PROBE
-#define RP_SPLIT_PROBE 0   // 1: timing probe, the split pass's source loads replaced by arithmetic (A/B builds only)
-#endif
 __device__ __forceinline__ u32 rp_ror1(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x13C, 0xF, 0xF, false); }
 
 template <int G, int PP, int NT, typename EF>
@@ -764,7 +746,7 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
     unsigned short *CODE = (unsigned short *)smem;   // G HP codes (over the exchange slots)
     Pr x[G][R];
     u32 *EDGE = SLT + G;   // rp_shift_all's lane-63 table (rp_lds)
-    if ((DIR == 0 && GX && RP_GX_LOAD) || LTW) {   // MFA twiddle 2^(tw0 + s twst) of slot s (README:89), so every level is pair-aligned:
+    if ((DIR == 0 && GX) || LTW) {   // MFA twiddle 2^(tw0 + s twst) of slot s (README:89), so every level is pair-aligned:
         // whole pairs by the rotated load, the rest by neighbour pairs in registers
         auto ef = [&](int i) -> u32 { return rp_uniform(EXPT[i]); };
         const RpCodes cd = rp_codes_load<G, PP>(st, SLT, t);
@@ -802,7 +784,7 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
         // consecutive threads, all slots' loads in flight at once, parked in the exchange slots; each
         // thread then reads its three limbs per pair back from LDS
         constexpr int SWP = l / 4 + 2, SW = 2 * SWP, KR = (G * SWP + NT - 1) / NT;
-        constexpr bool STAGE = RP_SPLIT_LDS && (size_t)G * SW * 8 <= (size_t)NX * RX<PP>::SB;
+        constexpr bool STAGE = (size_t)G * SW * 8 <= (size_t)NX * RX<PP>::SB;
         if (STAGE && !a.src_chunk) {
             u64 *S = (u64 *)smem;
             const long nsv = a.nsrc[op];
@@ -869,21 +851,14 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
                     const long q = (long)(off >> 6);
                     const long ns = left ? a.nsrc[op] : 0;
                     const SrcSlice sv{a.src_chunk, a.jNC, a.sub_off};
-#if RP_SPLIT_PROBE   // timing probe (A/B builds only, wrong products): the split pass without its source loads
-                    const u64 x0 = left ? (u64)q * 0x9e3779b97f4a7c15ull : 0, x1 = x0 ^ (u64)j, x2 = x1 + 1;
-#else
                     const u64 x0 = src_limb(src, ns, sv, j, a.bits1, q), x1 = src_limb(src, ns, sv, j, a.bits1, q + 1),
                               x2 = src_limb(src, ns, sv, j, a.bits1, q + 2);
-#endif
                     x[i][r] = split_pair(x0, x1, x2, (int)(off & 63), left);
                 }
             }
         }
     }
     RP_STAMP(1);
-    if (DIR == 0 && GX && !RP_GX_LOAD) {   // (A/B variant) the MFA twiddle through LDS after a plain load
-        rp_rot_all<G, PP, NX, NT>(x, X, [&](int s) -> u32 { return rp_uniform(EXPT[s]); }, N, t);
-    }
 
     // ---- levels ----------------------------------------------------------------------
 #pragma unroll
@@ -902,7 +877,7 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
                 // bit: x + 0 and x - 0 = x + ~0 + 1 both leave the five words of x as they are.  Not at
                 // l = 4096 with two levels (16 limb pairs per coefficient and thread): the branch put
                 // 24-28 B of scratch into that kernel, and all it saves is ten VALU operations a pair
-                constexpr bool L0COPY = RP_SPLIT_ZSKIP && RP_SPLIT_L0COPY && SPLIT && !(PP == 4 && LOGG == 2);
+                constexpr bool L0COPY = SPLIT && !(PP == 4 && LOGG == 2);
                 if (L0COPY && zero_in(k)) {
 #pragma unroll
                     for (int r = 0; r < R; ++r) x[k][r] = x[i][r];
@@ -928,10 +903,10 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
         // of each other (rp_class_single; the pending exponents differ, but they live in EXPT, not in
         // the registers): only the lowest is published, and every pair of the class reads that one
         // exchange slot with its own exponent.  xs(pi): the exchange slot pair pi reads (uniform).
-        auto pz = [&](int k) -> bool { return RP_SPLIT_ZSKIP && SPLIT && zero_in(k & ((1 << (LOGG - li)) - 1)); };
+        auto pz = [&](int k) -> bool { return SPLIT && zero_in(k & ((1 << (LOGG - li)) - 1)); };
         auto xs = [&](int pi, int k) -> int {
             int rep = k;
-            if (RP_SPLIT_ZSKIP && RP_SPLIT_PUB1 && SPLIT && rp_class_single(LOGG, li, nlive, k, rep)) return rp_pair_of(LOGG, li, rep);
+            if (SPLIT && rp_class_single(LOGG, li, nlive, k, rep)) return rp_pair_of(LOGG, li, rep);
             return pi;
         };
         const int tl = rp_launder(t);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Static figures of the pointwise kernels from `hipcc -S --cuda-device-only` output of pwss.hip /
-pwsq.hip: per kernel the register and scratch sizes of the code object's metadata and the counts
-of the instructions the wrap selects of pw_combine turn into.
+"""Static figures of the kernels (every __global__ k_*) in `hipcc -S --cuda-device-only` output, of
+pwss.hip / pwsq.hip first of all: per kernel the register and scratch sizes of the code object's
+metadata and the counts of the instructions the wrap selects of pw_combine turn into.
 
     pw_isa_stats.py LABEL=file.s [LABEL=file.s ...]
 
@@ -11,14 +11,22 @@ import hashlib
 import re
 import sys
 
-KERN = re.compile(r"^(_Z\d+k_pws[sq]ILi\d+ELi\d+ELi\d+E\w+):\s*(;.*)?$")
+KERN = re.compile(r"^(_Z\d+k_\w+):\s*(;.*)?$")
 PATS = [("v_cndmask", r"v_cndmask"), ("v_cmp", r"v_cmpx?_"), ("ds_read", r"ds_read"), ("ds_write", r"ds_write"),
         ("v_alignbit", r"v_alignbit"), ("s_nop", r"s_nop"), ("valu", r"v_"), ("all", r"[a-z]")]
 
 
 def demangle(sym):
-    m = re.match(r"_Z\d+(k_pws[sq])ILi(\d+)ELi(\d+)ELi(\d+)E", sym)
-    return "%s<%s,%s,%s>" % m.groups()
+    """k_name<a,b,...> for integer and bool template arguments, k_name without; else the symbol"""
+    n = int(re.match(r"_Z(\d+)", sym).group(1))
+    at = sym.index("k_")
+    name, rest = sym[at:at + n], sym[at + n:]
+    if not rest.startswith("I"):
+        return name
+    m = re.match(r"I((?:L[a-z]n?\d+E)+)E", rest)
+    if not m:
+        return sym
+    return "%s<%s>" % (name, ",".join(a.replace("n", "-") for a in re.findall(r"L[a-z](n?\d+)E", m.group(1))))
 
 
 def parse(path):
@@ -39,7 +47,7 @@ def parse(path):
             elif s and not s.startswith((";", ".")) and not s.endswith(":"):
                 body.append(re.sub(r"\s*;.*$", "", s))
             continue
-        m = re.match(r"\s+\.name:\s+(_Z\d+k_pws\S+)", line)
+        m = re.match(r"\s+\.name:\s+(_Z\d+k_\w+)", line)
         if m and not m.group(1).endswith(".kd"):
             mname = demangle(m.group(1))
         for key in ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size", "vgpr_spill_count"):
@@ -59,9 +67,10 @@ def main():
     data = {lab: parse(p) for lab, p in sets}
     kernels = sorted({k for c, _ in data.values() for k in c})
     cols = ["vgpr", "scratch", "lds_static"] + [k for k, _ in PATS]
-    print("%-18s %-8s " % ("kernel", "build") + " ".join("%10s" % c for c in cols) + "  same_code")
+    wk = max([18] + [len(k) for k in kernels])
+    print("%-*s %-8s " % (wk, "kernel", "build") + " ".join("%10s" % c for c in cols) + "  same_code")
     for k in kernels:
-        hashes = {data[lab][0][k]["hash"] for lab, _ in sets if k in data[lab][0]}
+        hashes = {data[lab][0][k]["hash"] if k in data[lab][0] else None for lab, _ in sets}   # None: not in that build
         for lab, _ in sets:
             c, meta = data[lab]
             if k not in c:
@@ -69,7 +78,7 @@ def main():
             m = meta.get(k, {})
             row = [m.get("vgpr_count", -1), m.get("private_segment_fixed_size", -1), m.get("group_segment_fixed_size", -1)]
             row += [c[k][n] for n, _ in PATS]
-            print("%-18s %-8s " % (k, lab) + " ".join("%10d" % v for v in row) + ("  yes" if len(hashes) == 1 else "  no"))
+            print("%-*s %-8s " % (wk, k, lab) + " ".join("%10d" % v for v in row) + ("  yes" if len(hashes) == 1 else "  no"))
 
 
 if __name__ == "__main__":

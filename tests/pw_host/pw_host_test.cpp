@@ -19,7 +19,7 @@ template <int M> int run() {
     mpz_set_ui(p, 1); mpz_mul_2exp(p, p, 64 * M); mpz_add_ui(p, p, 1);
     int bad = 0;
     for (int it = 0; it < 20000; ++it) {
-        // own value (L, T); partner q published as words (pw_publish's layout, 2M + 2 rows)
+        // own value (L, T); partner q published as words (pw_publish_words' layout, 2M + 2 rows)
         u64 L[M], Lq[M]; int T = (int)(rng() % 401) - 200, Tq = (int)(rng() % 401) - 200;
         for (int j = 0; j < M; ++j) { L[j] = rng(); Lq[j] = rng(); }
         if (it % 7 == 3) for (int j = 0; j < M; ++j) Lq[j] = it % 2 ? 0 : ~0ull;   // pw_norm wraps

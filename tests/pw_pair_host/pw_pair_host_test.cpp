@@ -4,7 +4,7 @@
 // bit-identical L, T, S to the per-word pw_combine<M, LK> on the same buffer -- rows 0 .. 2M-1
 // the partner's words, row 2M their ~word0, everything else random -- for M = 10 and 18 at
 // LK = 8 (the shapes k_pwss / k_pwsq run it at).  One case publishes a wrong row 2M and must
-// differ: the row is used.  The same for the groups of four of the A/B build (-DPW_GROUP=4), on a
+// differ: the row is used.  The same for the groups of four (the shipped K = 256 form, pw_group), on a
 // buffer whose rows 2M .. 2M+2 hold ~word0 .. ~word2.
 // Built by __graft_entry__.build() (tests/pw_pair_host/Makefile), run by tests/test_pw_pair_host.py.
 #include "pkernels.hpp"

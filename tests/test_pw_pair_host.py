@@ -21,5 +21,5 @@ def test_paired_combine_equals_per_word():
     p = subprocess.run([EXE], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and p.stdout.strip().endswith("OK"), p.stdout + p.stderr
     for M in (10, 18):
-        for form in ("pair", "quad"):   # quad: the groups of four of the A/B build (-DPW_GROUP=4)
+        for form in ("pair", "quad"):   # quad: the groups of four (the shipped K = 256 form, pw_group)
             assert re.search(r"M=%d %s combine cases=\d+ bad=0 wrong_row_unnoticed=0" % (M, form), p.stdout), p.stdout
