@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 4
+#define MPFFT_VERSION 5
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -152,6 +152,60 @@ int mpfft_mulmod_choose(long L, unsigned long *depth, unsigned long *w);
 /* For a caller free to choose the modulus: every candidate's smallest valid L >= min_L (a
  * multiple of its granularity 2n / 64), and of those the (L, depth, w) of least predicted time. */
 int mpfft_mulmod_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w);
+
+/* ---- multiplication by a precomputed operand (MPFFT_VERSION 5): for callers that multiply many
+ * numbers by the same one (Newton and Barrett steps against a fixed modulus or its inverse, powers
+ * of a fixed base, evaluation against a constant).  mpfft_precomp_device runs operand 2's forward
+ * stages once -- split, forward columns, forward rows, and on the nested pointwise plans the
+ * inner forward transform of every slot (k_pwsx) -- into a cache; mpfft_mul_precomp_device then
+ * computes r[0 .. n1 + n2) = i1 * (the cached i2) with operand 1's forward stages alone, the
+ * pointwise reading the cache (k_pwsp, or the other pointwise kernels with their B pointers aimed
+ * into it), and the multiply's inverse, scaling and combine unchanged: the same exact product.
+ * The cache: on nested plans (coefficients of 2048 or 4096 limbs, 1024 under
+ * MPFFT_POINTWISE=pwss) one record of K (8 M + 4) bytes per live slot -- 21 504 / 37 888 /
+ * 83 968 B at l = 1024 / 2048 / 4096, 2.3-2.6 x the slot itself; elsewhere the live slots of
+ * operand 2's transformed coefficient arrays (limbs and carry limbs).  It is bound to
+ * (n1, n2, depth, w) -- the truncation depends on both sizes --, to the MPFFT_POINTWISE selection in
+ * force when it was made and to the library version (do not store it); it is plain,
+ * position-independent device memory, only read by a multiply, so multiplies on different
+ * streams with different workspaces may share one cache.
+ * Parameter validation and status codes are those of mpfft_check_params(n1, n2, depth, w); a
+ * workspace or cache that is too small returns MPFFT_ENOMEM.
+ * Not covered: the sqrt2 front end (new_mpn_mul6), the products mod 2^B + 1, the sharded /
+ * multi-GPU entries and mpfft_set_devices routing -- these always run on the calling thread's
+ * device. */
+size_t mpfft_precomp_bytes(long n1, long n2, unsigned long depth, unsigned long w);   /* 0 on invalid parameters */
+/* d_i2[0 .. n2) -> d_pre, queued on `stream`; d_ws holds mpfft_workspace_bytes(n1, n2, depth, w). */
+int mpfft_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t *d_i2, long n1, long n2,
+                         unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* mpfft_workspace_bytes(n1, n2, depth, w) less operand B's limb, top and carry-mask arrays. */
+size_t mpfft_mul_precomp_workspace_bytes(long n1, long n2, unsigned long depth, unsigned long w);
+/* d_r = d_i1 * cached operand, queued on `stream` and not synchronised; d_ws holds
+ * mpfft_mul_precomp_workspace_bytes bytes; d_pre is only read. */
+int mpfft_mul_precomp_device(uint64_t *d_r, const uint64_t *d_i1, long n1, const void *d_pre, size_t pre_bytes, long n2,
+                             unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* As mpfft_stage_kernels with one extra leading field: what writes the cache ("k_pwsx<M>..." with
+ * the pointwise's pair / quad suffix, or "copy"), then the seven stages of a multiply against it,
+ * the pointwise "k_pwsp<M>..." on nested plans and "<kernel> (B cached)" elsewhere. */
+int mpfft_precomp_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len);
+/* (tests) One stage of the precomputation on the multiply's workspace: MPFFT_STAGE_FWD_COLUMNS and
+ * MPFFT_STAGE_FWD_ROWS on operand 2 alone (every row level: none is fused), MPFFT_STAGE_PRE_STORE:
+ * operand B's row arrays -> d_pre.  MPFFT_EINVAL on any other stage. */
+#define MPFFT_STAGE_PRE_STORE 8
+int mpfft_precomp_stage(int stage, void *d_pre, size_t pre_bytes, const uint64_t *d_i2, long n1, long n2,
+                        unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* (tests) One MPFFT_STAGE_* stage of the multiply on the workspace without B's arrays, operand 1
+ * only; MPFFT_STAGE_POINTWISE reads d_pre. */
+int mpfft_mul_precomp_stage(int stage, const uint64_t *d_i1, const void *d_pre, size_t pre_bytes, uint64_t *d_r, long n1,
+                            long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* Host pointers: an opaque handle that owns the device cache of i2[0 .. n2) for products with
+ * n1-limb operands, bound to the HIP device current at creation.  mpfft_mul_precomp_ex returns
+ * MPFFT_EINVAL for another n1, on another device, or after MPFFT_POINTWISE changed the kernel
+ * family.  r may not overlap i1. */
+typedef struct mpfft_pre mpfft_pre;
+int mpfft_precomp_create(mpfft_pre **out, const uint64_t *i2, long n2, long n1, unsigned long depth, unsigned long w);
+int mpfft_mul_precomp_ex(uint64_t *r, const uint64_t *i1, long n1, const mpfft_pre *pre);
+void mpfft_precomp_destroy(mpfft_pre *pre);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity
@@ -352,7 +406,9 @@ int mpfft_set_devices(int ngpus, const int *devices, long min_l);
 int mpfft_last_ngpus(void);
 
 /* Stage profiling of the whole-multiply entries (new_mpn_mul, mpfft_mul_ex,
- * mpfft_mul_device, the squares mpfft_sqr_ex / mpfft_sqr_device, and the products mod 2^B + 1, where
+ * mpfft_mul_device, the squares mpfft_sqr_ex / mpfft_sqr_device, the multiplies against a precomputed
+ * operand and the precomputation itself -- its last stage is the store into the cache, the four
+ * after it read 0 --, and the products mod 2^B + 1, where
  * the weight launch counts with the forward columns, the un-weight is the scale stage and the
  * negacyclic combine the combine stage): between begin and end, each of the next max_calls multiplies
  * records a HIP event on its own stream at every stage boundary (no other change to

@@ -27,6 +27,7 @@ _lib = None
 
 STAGE_FWD_COLUMNS, STAGE_FWD_ROWS, STAGE_POINTWISE, STAGE_INV_ROWS, STAGE_INV_COLUMNS, \
     STAGE_SCALE, STAGE_COMBINE, STAGE_FOLD_COMBINE = range(8)
+STAGE_PRE_STORE = 8   # precomp_stage: operand B's row arrays -> the cache
 # (tests) or-ed onto STAGE_INV_ROWS / _INV_COLUMNS / _SCALE: the stage as the whole multiply drives it
 STAGE_DRIVEN = 0x100
 
@@ -210,6 +211,28 @@ def lib():
             h.mpfft_mulmod_choose.restype = ctypes.c_int
             h.mpfft_mulmod_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
             h.mpfft_mulmod_next_size.restype = ctypes.c_int
+        if hasattr(h, "mpfft_precomp_device"):   # MPFFT_VERSION 5 (older libraries in A/B runs lack them)
+            _sz = ctypes.c_size_t
+            h.mpfft_precomp_bytes.argtypes = [_L, _L, _UL, _UL]
+            h.mpfft_precomp_bytes.restype = _sz
+            h.mpfft_precomp_device.argtypes = [_vp, _sz, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_precomp_device.restype = ctypes.c_int
+            h.mpfft_mul_precomp_workspace_bytes.argtypes = [_L, _L, _UL, _UL]
+            h.mpfft_mul_precomp_workspace_bytes.restype = _sz
+            h.mpfft_mul_precomp_device.argtypes = [_vp, _vp, _L, _vp, _sz, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_mul_precomp_device.restype = ctypes.c_int
+            h.mpfft_precomp_stage_kernels.argtypes = [_L, _L, _UL, _UL, ctypes.c_char_p, _sz]
+            h.mpfft_precomp_stage_kernels.restype = ctypes.c_int
+            h.mpfft_precomp_stage.argtypes = [ctypes.c_int, _vp, _sz, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_precomp_stage.restype = ctypes.c_int
+            h.mpfft_mul_precomp_stage.argtypes = [ctypes.c_int, _vp, _vp, _sz, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_mul_precomp_stage.restype = ctypes.c_int
+            h.mpfft_precomp_create.argtypes = [ctypes.POINTER(_vp), _u64p, _L, _L, _UL, _UL]
+            h.mpfft_precomp_create.restype = ctypes.c_int
+            h.mpfft_mul_precomp_ex.argtypes = [_u64p, _u64p, _L, _vp]
+            h.mpfft_mul_precomp_ex.restype = ctypes.c_int
+            h.mpfft_precomp_destroy.argtypes = [_vp]
+            h.mpfft_precomp_destroy.restype = None
         _lib = h
     return _lib
 
@@ -523,6 +546,129 @@ def sqr_workspace_views(ws, n, depth, w):
     dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
     top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
     return dig, top
+
+
+# ---- multiplication by a precomputed operand (mpfft_precomp_*, mpfft_mul_precomp_*, include/mpfft.h):
+# operand 2's forward transform is computed once into a cache, bound to (n1, n2, depth, w) ----
+
+def precomp_bytes(n1, n2, depth, w):
+    return int(lib().mpfft_precomp_bytes(n1, n2, depth, w))
+
+
+def alloc_precomp(n1, n2, depth, w, device="cuda"):
+    import torch
+    nb = precomp_bytes(n1, n2, depth, w)
+    if nb == 0:
+        raise MpfftError(check_params(n1, n2, depth, w), "precomp cache")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def precomp_device(pre, d_i2, n1, n2, depth, w, ws, stream=None):
+    """d_i2[:n2] -> the cache `pre` (alloc_precomp) for products with n1-limb operands; ws is the
+    multiply's workspace (alloc_workspace); queued on `stream`, not synchronised."""
+    rc = lib().mpfft_precomp_device(_ptr(pre), _nbytes(pre), _ptr(d_i2), n1, n2, depth, w, _ptr(ws), _nbytes(ws),
+                                    _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_precomp_device")
+
+
+def mul_precomp_workspace_bytes(n1, n2, depth, w):
+    return int(lib().mpfft_mul_precomp_workspace_bytes(n1, n2, depth, w))
+
+
+def alloc_workspace_mul_precomp(n1, n2, depth, w, device="cuda"):
+    import torch
+    nb = mul_precomp_workspace_bytes(n1, n2, depth, w)
+    if nb == 0:
+        raise MpfftError(check_params(n1, n2, depth, w), "mul_precomp workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def mul_precomp_device(d_r, d_i1, n1, pre, n2, depth, w, ws, stream=None):
+    """d_r[:n1+n2] = d_i1[:n1] * the operand cached in `pre` (only read); ws from
+    alloc_workspace_mul_precomp; queued on `stream`, not synchronised."""
+    rc = lib().mpfft_mul_precomp_device(_ptr(d_r), _ptr(d_i1), n1, _ptr(pre), _nbytes(pre), n2, depth, w, _ptr(ws),
+                                        _nbytes(ws), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_mul_precomp_device")
+
+
+PRECOMP_STAGE_NAMES = ("precomp",) + STAGE_NAMES
+
+
+def precomp_stage_kernels(n1, n2, depth, w):
+    """dict: 'precomp' -> what writes the cache (k_pwsx<M>... or 'copy'), then stage -> the kernel a
+    multiply against the cache launches (the pointwise: k_pwsp<M>... or '<kernel> (B cached)')"""
+    buf = ctypes.create_string_buffer(640)
+    rc = lib().mpfft_precomp_stage_kernels(n1, n2, depth, w, buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_precomp_stage_kernels")
+    return dict(zip(PRECOMP_STAGE_NAMES, buf.value.decode().split(";")))
+
+
+def precomp_stage(which, pre, d_i2, n1, n2, depth, w, ws, stream=None):
+    """One stage of the precomputation on the multiply's workspace: STAGE_FWD_COLUMNS / _FWD_ROWS on
+    operand 2, STAGE_PRE_STORE (B's row arrays -> pre)."""
+    rc = lib().mpfft_precomp_stage(which, _ptr(pre), _nbytes(pre) if pre is not None else 0, _ptr(d_i2), n1, n2,
+                                   depth, w, _ptr(ws), _nbytes(ws), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_precomp_stage({which})")
+
+
+def mul_precomp_stage(which, d_i1, pre, d_r, n1, n2, depth, w, ws, stream=None):
+    """One stage of the multiply on the workspace without B's arrays; STAGE_POINTWISE reads pre."""
+    rc = lib().mpfft_mul_precomp_stage(which, _ptr(d_i1), _ptr(pre), _nbytes(pre) if pre is not None else 0,
+                                       _ptr(d_r), n1, n2, depth, w, _ptr(ws), _nbytes(ws), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_mul_precomp_stage({which})")
+
+
+class Precomp:
+    """Host-pointer handle (mpfft_precomp_create): owns the device cache of operand `i2` for
+    products with n1-limb operands at (depth, w), on the HIP device current at creation.  A context
+    manager; close() frees the cache."""
+
+    def __init__(self, i2, n1, depth, w):
+        i2 = np.ascontiguousarray(i2, dtype=np.uint64)
+        self.n1, self.n2, self.depth, self.w = n1, len(i2), depth, w
+        h = _vp()
+        rc = lib().mpfft_precomp_create(ctypes.byref(h), _p(i2), len(i2), n1, depth, w)
+        if rc:
+            raise MpfftError(rc, f"precomp_create(n1={n1}, n2={len(i2)}, depth={depth}, w={w})")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            lib().mpfft_precomp_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mul_precomp(i1, pre):
+    """i1 * (the operand of the Precomp handle) as a new uint64 array of n1 + n2 limbs."""
+    if pre._h is None:
+        raise ValueError("the Precomp handle is closed")
+    i1 = np.ascontiguousarray(i1, dtype=np.uint64)
+    r = np.zeros(len(i1) + pre.n2, dtype=np.uint64)
+    rc = lib().mpfft_mul_precomp_ex(_p(r), _p(i1), len(i1), pre._h)
+    if rc:
+        raise MpfftError(rc, f"mul_precomp(n1={len(i1)})")
+    return r
 
 
 # ---- products mod 2^B + 1, B = 64 L (mpfft_mulmod_*, include/mpfft.h): operands and result are

@@ -84,6 +84,11 @@ struct Exec {
     u32 *zflags = nullptr;   // non-null: the first forward column pass clears the combine's look-back flags
     long zflags_n = 0;       // (u32 words), so combine_single needs no separate fill launch
     int in_rows = 0;         // non-zero: inputs live in column rows [0, in_rows) (default: the trunc rows)
+    // multiplication by a precomputed operand: the cache of operand B (plan_pre_bytes).  On a
+    // Plan::pre plan the pointwise reads it (use_pre); pre_make: operand B's forward stages run
+    // alone on the multiply's plan and precomp_store() writes it
+    unsigned char *pre = nullptr;
+    bool pre_make = false;
     bool defer_double = false;   // itft's top-level doubling is left to scale() (rows [dbl_lo, dbl_hi): 2^-depth)
     bool fold = false;           // f4 (P.fold): 2^-(depth+1) in the last inverse row pass, no scale(), combine_fold()
     bool fuse_row_last = false;  // the row DIF's last level runs inside the pointwise (k_pwss PAIR)
@@ -192,11 +197,27 @@ struct Exec {
             col.top[1] = col.top[0];
             col.cb[1] = col.cb[0];
         }
+        if (P.pre) {   // no B arrays: operand 1 is read from the cache by the pointwise alone (use_pre)
+            col.dig[1] = nullptr;
+            col.top[1] = nullptr;
+            col.cb[1] = nullptr;
+        }
         row = col;
         if (P.has_c) {
             cview.dig[0] = (u64 *)(ws + P.off_digC);
             cview.top[0] = (int *)(ws + P.off_topC);
             cview.cb[0] = (u64 *)(ws + P.off_cbC);
+        }
+    }
+
+    // a Plan::pre plan's operand B: on the families that read B's row arrays, the cache holds their
+    // live slots (limbs, then carry limbs; canonical, no carry masks); k_pwsp takes the records
+    void use_pre(const void *d_pre)
+    {
+        pre = (unsigned char *)d_pre;
+        if (P.pre && pre && !pwss_active()) {
+            row.dig[1] = (u64 *)pre;
+            row.top[1] = (int *)(pre + plan_pre_dig_bytes(P));
         }
     }
 
@@ -548,7 +569,8 @@ struct Exec {
     {
         static const bool off = [] { const char *e = diag_env("MPFFT_FUSE_ROW"); return e && !strcmp(e, "0"); }();
         const int f = P.fuse_rows;
-        return fuse_row_last && !off && f && cview.dig[0] && pw_pair_kernel(P.l, f) && ccb >= (1 << f) ? f : 0;
+        // (k_pwsx writes to the cache: precomputing needs no C arrays)
+        return fuse_row_last && !off && f && (cview.dig[0] || pre_make) && pw_pair_kernel(P.l, f) && ccb >= (1 << f) ? f : 0;
     }
 
     int row_levels() const { return P.lbC - row_fused(); }
@@ -575,20 +597,26 @@ struct Exec {
 
     long pw_count = 0;   // > 0: the pointwise covers this many slots from the row views (a row chunk of one column block)
 
-    // the nested negacyclic pointwise (pkernels.hpp): k_pwss, or k_pwsq on a squaring plan
+    // the nested negacyclic pointwise (pkernels.hpp): k_pwss, k_pwsq on a squaring plan, or k_pwsp
+    // against the cache on a Plan::pre plan
     int pointwise_nested(long cnt)
     {
         const int lk = pwss_lk_of(P.l), M = pw_inner_limbs(P.l, lk), fz = row_fused();
         pw_fn f = pw_get(M, lk, fz);
         pw_sq_fn fs = P.sqr ? pw_get_sqr(M, lk, fz) : nullptr;
+        pw_mulpre_fn fp = P.pre ? pw_get_mulpre(M, lk, fz) : nullptr;
         if (!f || (P.sqr && !fs)) return MPFFT_EUNSUPPORTED;   // a missing squaring instance is an error
+        if (P.pre && (!fp || !pre)) return MPFFT_EUNSUPPORTED;  // and so is a missing cached one
         const size_t lds = pw_lds(M, 1 << lk, (int)P.l);
         const dim3 grid((unsigned)cnt), block(1u << lk);
         static const bool stamps = diag_env("MPFFT_PW_STAMPS") != nullptr;
         Stamps st;   // diagnostics only
         int rc;
         if (stamps && (rc = stamps_begin(st, (size_t)cnt))) return rc;
-        if (fs)   // squaring plan: the same grid, block and LDS
+        if (fp)   // against the cache: the same grid, block and LDS
+            rc = launch(fp, grid, block, lds, row.dig[0], row.cb[0], row.top[0], (const unsigned char *)pre, (int)P.l,
+                        cview.dig[0], cview.cb[0], cview.top[0], st.d);
+        else if (fs)   // squaring plan: the same grid, block and LDS
             rc = launch(fs, grid, block, lds, row.dig[0], row.cb[0], row.top[0], (int)P.l, cview.dig[0], cview.cb[0],
                         cview.top[0], st.d);
         else
@@ -610,10 +638,29 @@ struct Exec {
         return MPFFT_OK;
     }
 
+    // operand B's live slots in the row arrays -> the cache (pre_make): k_pwsx on nested plans (the
+    // row levels the plan fuses run in its loaders), else a copy of the limbs and carry limbs
+    int precomp_store()
+    {
+        const long cnt = (long)rcount * P.NC;
+        if (!pre) return MPFFT_EINVAL;
+        if (!pwss_active()) {
+            HIPCHK(hipMemcpyAsync(pre, row.dig[1], plan_pre_dig_bytes(P), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(pre + plan_pre_dig_bytes(P), row.top[1], (size_t)cnt * 4, hipMemcpyDeviceToDevice, s));
+            return MPFFT_OK;
+        }
+        const int lk = pwss_lk_of(P.l), M = pw_inner_limbs(P.l, lk), fz = row_fused();
+        pw_pre_fn f = pw_get_pre(M, lk, fz);
+        if (!f) return MPFFT_EUNSUPPORTED;
+        return launch(f, dim3((unsigned)cnt), dim3(1u << lk), pw_lds(M, 1 << lk, (int)P.l), (const u64 *)row.dig[1],
+                      (const u64 *)row.cb[1], (const int *)row.top[1], (int)P.l, pre, (unsigned long long *)nullptr);
+    }
+
     int pointwise()
     {
         const long cnt = pw_count > 0 ? pw_count : (long)rcount * P.NC;
         if (cnt == 0) return MPFFT_OK;
+        if (P.pre && !pre) return MPFFT_EINVAL;
         // Squaring plans reach the four families after the nested one with A's arrays as B as well
         // (Exec::single).  That is safe in place: in each of k_pwm2, k_pwm, k_pw and k_pointwise a
         // thread reads topB[slot] and its limbs of B at the very point where it reads topA[slot]

@@ -191,20 +191,28 @@ struct HostB {
     hipEvent_t ready;   // recorded on cs after the copy
 };
 
-// operand 0 alone on a squaring plan (one grid row), else both operands in one launch
-static int fwd_nops(const Plan &P) { return P.sqr ? 1 : 2; }
-static int fwd_op(const Plan &P) { return P.sqr ? 0 : -1; }
+// operand 0 alone on a squaring plan and against a precomputed operand (one grid row), else both
+// operands in one launch
+static int fwd_nops(const Plan &P) { return P.sqr || P.pre ? 1 : 2; }
+static int fwd_op(const Plan &P) { return P.sqr || P.pre ? 0 : -1; }
 
 // The whole single-GPU product.  A squaring plan (make_plan_sqr) takes its operand as d_i1 and
 // d_i2 alike: one split, one forward column and row transform (that pass still clears the
 // combine flags), the pointwise in squaring mode (k_pwsq, or the other families with B = A),
 // then the multiply's inverse, scaling and combine unchanged.
+// d_pre: the cache of a precomputed operand B (plan_pre_bytes).  On a Plan::pre plan (make_plan_pre)
+// the product is d_i1 times the cached operand: operand 0's forward stages, the pointwise against
+// the cache, the rest unchanged.  pre_make (the multiply's own plan and workspace): operand B's
+// forward columns and rows alone, then its row arrays into the cache (Exec::precomp_store) -- the
+// stage marks after that one coincide.
 static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, unsigned char *ws, hipStream_t s,
-                   const HostB *hb = nullptr)
+                   const HostB *hb = nullptr, unsigned char *d_pre = nullptr, bool pre_make = false)
 {
     if (P.sqrt2) return run_all6(P, d_r, d_i1, d_i2, ws, s);
     Exec X(P, s);
     X.single(ws);
+    X.use_pre(d_pre);
+    X.pre_make = pre_make;
     X.zflags = X.comb_flags(ws);
     X.zflags_n = X.comb_flag_words(P, P.total);
     X.drive_single();
@@ -212,6 +220,16 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
     ProfCall pc;
     int rc;
     pc.mark(0, s);
+    if (pre_make) {
+        // (operand B as both sources: its own zero bound prunes the split pass, operand 0 is not read)
+        if ((rc = X.fwd_columns(d_i2, P.n2, d_i2, P.n2, 1, 1))) return rc;
+        pc.mark(1, s);
+        if ((rc = X.fwd_rows(1, 1))) return rc;
+        pc.mark(2, s);
+        rc = X.precomp_store();
+        for (int k = 3; k <= MPFFT_NSTAGES; ++k) pc.mark(k, s);
+        return rc;
+    }
     if (hb && hb->h) {   // operand 1's forward transform overlaps operand 2's H2D copy
         // kernels first: a copy from pageable memory may hold the calling thread until it is done
         if ((rc = X.fwd_columns(d_i1, P.n1, d_i2, P.n2, 1, 0))) return rc;
@@ -305,7 +323,8 @@ static std::string fwd_columns_launches(const Plan &P)
 }
 
 // Which kernel carries each stage of plan P (the same decisions Exec makes), seven fields joined
-// by ';'.  On a squaring plan the pointwise is named k_pwsq<M>..., or "<kernel> (B = A)".
+// by ';'.  On a squaring plan the pointwise is named k_pwsq<M>..., or "<kernel> (B = A)"; against
+// a precomputed operand (Plan::pre) k_pwsp<M>..., or "<kernel> (B cached)".
 static std::string stage_kernel_names(const Plan &P)
 {
     const char *pass = P.big ? (P.rpass ? "k_rpass" : "k_bpass") : (P.wave && P.lds) ? "k_lpass" : P.wave ? "k_wpass" : "k_pass";
@@ -316,11 +335,11 @@ static std::string stage_kernel_names(const Plan &P)
         const int lk = pwss_lk_of(P.l);
         const char *fz = diag_env("MPFFT_FUSE_ROW");
         const bool fused = P.has_c && !(fz && !strcmp(fz, "0"));   // as Exec::row_fused() in run_all
-        snprintf(pw, sizeof pw, "%s<%d>%s (nested negacyclic, K=%d)", P.sqr ? "k_pwsq" : "k_pwss", pw_inner_limbs(P.l, lk),
+        snprintf(pw, sizeof pw, "%s<%d>%s (nested negacyclic, K=%d)", P.sqr ? "k_pwsq" : P.pre ? "k_pwsp" : "k_pwss", pw_inner_limbs(P.l, lk),
                  !fused ? "" : P.fuse_rows == 2 ? " quad + last two row levels" : " pair + last row level", 1 << lk);
     } else {
         snprintf(pw, sizeof pw, "%s%s", fam == PWF_PWM2 ? "k_pwm2 (int8 MFMA)" : fam == PWF_PWM ? "k_pwm (int8 MFMA)"
-                                        : fam == PWF_PW ? "k_pw (VALU)" : "k_pointwise (VALU)", P.sqr ? " (B = A)" : "");
+                                        : fam == PWF_PW ? "k_pw (VALU)" : "k_pointwise (VALU)", P.sqr ? " (B = A)" : P.pre ? " (B cached)" : "");
     }
     const char *pair = P.rpass ? "k_rpair" : P.wave ? "k_wpair" : "k_pairop";
     const char *scale = P.fuse_scale ? "(fused into the last inverse column pass)"
@@ -355,6 +374,20 @@ static std::string stage_kernel_names(const Plan &P)
     return std::string(fwdc) + ';' + rows + ';' + pw + ';' + pass + ';' + invc + ';' + scale + ';' + comb;
 }
 
+// What writes the cache of a precomputed operand for the multiply's plan P: k_pwsx with the
+// pointwise's pair / quad suffix, or a copy of B's row arrays
+static std::string precomp_kernel_name(const Plan &P)
+{
+    if (pw_family(P) != PWF_NESTED) return "copy";
+    const int lk = pwss_lk_of(P.l);
+    const char *fz = diag_env("MPFFT_FUSE_ROW");
+    const bool fused = P.has_c && !(fz && !strcmp(fz, "0"));   // as stage_kernel_names
+    char pw[112];
+    snprintf(pw, sizeof pw, "k_pwsx<%d>%s (nested negacyclic, K=%d)", pw_inner_limbs(P.l, lk),
+             !fused ? "" : P.fuse_rows == 2 ? " quad + last two row levels" : " pair + last row level", 1 << lk);
+    return pw;
+}
+
 // a whole string into the caller's buffer, or MPFFT_EINVAL
 static int copy_out(const std::string &s, char *buf, size_t len)
 {
@@ -379,7 +412,7 @@ static void layout_out(const Plan &P, size_t *out)
 // One single-GPU stage (device pointers) on plan P; `ws` has P's workspace layout.  A squaring
 // plan's forward stages run operand 0 alone.
 static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const uint64_t *d_i2, uint64_t *d_r,
-                        void *d_ws, size_t ws_bytes, void *stream)
+                        void *d_ws, size_t ws_bytes, void *stream, const void *d_pre = nullptr)
 {
     const bool driven = (stage & MPFFT_STAGE_DRIVEN) != 0;   // (tests) the inverse stages as run_all drives them
     stage &= ~MPFFT_STAGE_DRIVEN;
@@ -389,6 +422,7 @@ static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const ui
     (void)hipGetLastError();
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
+    X.use_pre(d_pre);
     if (driven) {
         X.drive_single();
         if (stage == MPFFT_STAGE_SCALE) plan_dbl(P, &X.dbl_lo, &X.dbl_hi);
@@ -914,6 +948,172 @@ int mpfft_sqr_ex(uint64_t *r, const uint64_t *a, long n, unsigned long depth, un
     if ((rc = mul_host(P, r, a, n, a, n))) return rc;
     g_last_ngpus = 1;
     return MPFFT_OK;
+}
+
+// ---- multiplication by a precomputed operand: operand 2's forward transform is computed once
+// into a cache (run_all's pre_make mode on the multiply's plan), and each product against it runs
+// the multiply's driver on the plan without B's arrays (make_plan_pre), the pointwise reading the
+// cache.  Out of scope as for the squares: the sqrt2 front end, the mod 2^B + 1 entries, the
+// sharded and multi-GPU entries, mpfft_set_devices routing. -----------------------------------
+size_t mpfft_precomp_bytes(long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan(&P, n1, n2, depth, w)) return 0;
+    return plan_pre_bytes(P);
+}
+
+int mpfft_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t *d_i2, long n1, long n2, unsigned long depth,
+                         unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan(&P, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    return run_all(P, nullptr, nullptr, d_i2, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre, true);
+}
+
+size_t mpfft_mul_precomp_workspace_bytes(long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan_pre(&P, n1, n2, depth, w)) return 0;
+    return P.bytes;
+}
+
+int mpfft_mul_precomp_device(uint64_t *d_r, const uint64_t *d_i1, long n1, const void *d_pre, size_t pre_bytes, long n2,
+                             unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_pre(&P, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    return run_all(P, d_r, d_i1, d_i1, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre);
+}
+
+int mpfft_precomp_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
+{
+    Plan P, Q;
+    int rc = make_plan(&P, n1, n2, depth, w);
+    if (rc || (rc = make_plan_pre(&Q, n1, n2, depth, w))) return rc;
+    return copy_out(precomp_kernel_name(P) + ';' + stage_kernel_names(Q), buf, len);
+}
+
+int mpfft_precomp_stage(int stage, void *d_pre, size_t pre_bytes, const uint64_t *d_i2, long n1, long n2,
+                        unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan(&P, n1, n2, depth, w);
+    if (rc) return rc;
+    if (stage != MPFFT_STAGE_FWD_COLUMNS && stage != MPFFT_STAGE_FWD_ROWS && stage != MPFFT_STAGE_PRE_STORE)
+        return MPFFT_EINVAL;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (stage == MPFFT_STAGE_PRE_STORE && (!d_pre || pre_bytes < plan_pre_bytes(P))) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    Exec X(P, (hipStream_t)stream);
+    X.single((unsigned char *)d_ws);
+    X.use_pre(d_pre);
+    X.pre_make = true;
+    if (stage == MPFFT_STAGE_FWD_COLUMNS) return X.fwd_columns(d_i2, P.n2, d_i2, P.n2, 1, 1);
+    if (stage == MPFFT_STAGE_FWD_ROWS) return X.fwd_rows(1, 1);
+    return X.precomp_store();
+}
+
+int mpfft_mul_precomp_stage(int stage, const uint64_t *d_i1, const void *d_pre, size_t pre_bytes, uint64_t *d_r, long n1,
+                            long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_pre(&P, n1, n2, depth, w);
+    if (rc) return rc;
+    if ((stage & ~MPFFT_STAGE_DRIVEN) == MPFFT_STAGE_POINTWISE && (!d_pre || pre_bytes < plan_pre_bytes(P))) return MPFFT_ENOMEM;
+    return single_stage(P, stage, d_i1, d_i1, d_r, d_ws, ws_bytes, stream, d_pre);
+}
+
+// host pointers: the handle owns the device cache, made on the calling thread's device
+struct mpfft_pre {
+    int dev;
+    long n1, n2;
+    unsigned long depth, w;
+    int family;     // the pointwise family (MPFFT_POINTWISE) the cache was made for
+    void *d_pre;
+    size_t bytes;
+};
+
+// the calling thread's device context with its stream, locked by the caller through C->mu
+static int host_ctx(DevCtx **C, int *dev)
+{
+    int ndev = 0;
+    (void)hipGetLastError();
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
+    if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
+    *C = &g_dev[*dev];
+    return MPFFT_OK;
+}
+
+int mpfft_precomp_create(mpfft_pre **out, const uint64_t *i2, long n2, long n1, unsigned long depth, unsigned long w)
+{
+    if (!out) return MPFFT_EINVAL;
+    *out = nullptr;
+    Plan P;
+    int rc = make_plan(&P, n1, n2, depth, w), dev = 0;
+    if (rc) return rc;
+    DevCtx *Cp;
+    if ((rc = host_ctx(&Cp, &dev))) return rc;
+    DevCtx &C = *Cp;
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
+    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, (size_t)n2 * 8))) return rc;
+    mpfft_pre *h = new mpfft_pre{dev, n1, n2, depth, w, (int)pw_family(P), nullptr, plan_pre_bytes(P)};
+    if (hipMalloc(&h->d_pre, h->bytes) != hipSuccess) {
+        delete h;
+        return MPFFT_ENOMEM;
+    }
+    rc = hipMemcpyAsync(C.io, i2, (size_t)n2 * 8, hipMemcpyHostToDevice, C.stream) == hipSuccess ? MPFFT_OK : MPFFT_EHIP;
+    if (!rc) rc = run_all(P, nullptr, nullptr, C.io, C.ws, C.stream, nullptr, (unsigned char *)h->d_pre, true);
+    if (!rc && hipStreamSynchronize(C.stream) != hipSuccess) rc = MPFFT_EHIP;
+    if (rc) {
+        if (rc == MPFFT_EHIP) last_hip_error = hipGetLastError();
+        (void)hipFree(h->d_pre);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return MPFFT_OK;
+}
+
+int mpfft_mul_precomp_ex(uint64_t *r, const uint64_t *i1, long n1, const mpfft_pre *pre)
+{
+    if (!pre || n1 != pre->n1) return MPFFT_EINVAL;
+    Plan P;
+    int rc = make_plan_pre(&P, n1, pre->n2, pre->depth, pre->w), dev = 0;
+    if (rc) return rc;
+    if ((int)pw_family(P) != pre->family) return MPFFT_EINVAL;   // MPFFT_POINTWISE changed since the cache was made
+    DevCtx *Cp;
+    if ((rc = host_ctx(&Cp, &dev))) return rc;
+    if (dev != pre->dev) return MPFFT_EINVAL;
+    DevCtx &C = *Cp;
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
+    const long n2 = pre->n2;
+    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, (size_t)(2 * n1 + n2) * 8))) return rc;
+    u64 *d_i1 = C.io, *d_r = C.io + n1;
+    HIPCHK(hipMemcpyAsync(d_i1, i1, (size_t)n1 * 8, hipMemcpyHostToDevice, C.stream));
+    if ((rc = run_all(P, d_r, d_i1, d_i1, C.ws, C.stream, nullptr, (unsigned char *)pre->d_pre))) return rc;
+    HIPCHK(hipMemcpyAsync(r, d_r, (size_t)(n1 + n2) * 8, hipMemcpyDeviceToHost, C.stream));
+    HIPCHK(hipStreamSynchronize(C.stream));
+    g_last_ngpus = 1;
+    return MPFFT_OK;
+}
+
+void mpfft_precomp_destroy(mpfft_pre *pre)
+{
+    if (!pre) return;
+    if (pre->d_pre) (void)hipFree(pre->d_pre);
+    delete pre;
 }
 
 // ---- products mod 2^B + 1 (nega.hpp, make_plan_mod, run_all_mod).  Out of scope as for the

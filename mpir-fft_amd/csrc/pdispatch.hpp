@@ -18,6 +18,17 @@ size_t pw_lds(int M, int K, int l);
 typedef void (*pw_sq_fn)(uint64_t *, uint64_t *, int *, int, uint64_t *, uint64_t *, int *, unsigned long long *);
 pw_sq_fn pw_get_sqr(int M, int lk, int fuse = 0);
 
+// Multiplication by a precomputed operand (pwsp.hip), the same instances, LDS and launch shape:
+// k_pwsx<M, lk, fuse>: operand B's slots (through k_pwss's loaders for that fuse) -> the cache, one
+// record of pw_pre_record_bytes(M, K) bytes per slot; k_pwsp<M, lk, fuse>: A[slot] times record
+// `slot`, to A in place (fuse 0) or to C; nullptr if not built
+typedef void (*pw_pre_fn)(const uint64_t *, const uint64_t *, const int *, int, unsigned char *, unsigned long long *);
+pw_pre_fn pw_get_pre(int M, int lk, int fuse = 0);
+typedef void (*pw_mulpre_fn)(uint64_t *, uint64_t *, int *, const unsigned char *, int, uint64_t *, uint64_t *, int *,
+                             unsigned long long *);
+pw_mulpre_fn pw_get_mulpre(int M, int lk, int fuse = 0);
+size_t pw_pre_record_bytes(int M, int K);
+
 // Inner ring for a product mod 2^(64 l) + 1 cut into K = 2^lk pieces: the smallest even M
 // (limbs) with 64 M >= 2 (64 l / K) + lk + 4: the pair-fused inputs (pieces of x0 +- x1) are
 // below 2^(B+1) (1 + 2^-64) in magnitude, so |c_t| < K 2^(2B+2) (1 + 2^-62) < 2^(N'-1)

@@ -995,6 +995,27 @@ __device__ __forceinline__ unsigned pw_weight_exp(int t)
     return (((unsigned)t * W2) >> 1) + (((W2 & 1) && (t & 1)) ? NP / 4 : 0);   // < N' + N'/4
 }
 
+// Cache record of one slot of a precomputed operand (k_pwsx writes it, k_pwsp reads it): the
+// operand's pieces after the weight, the inner forward transform and pw_canon -- M rows of K
+// limbs, limb j of thread t at [j K + t] (a wave's loads and stores are consecutive 8-byte
+// words), then one meta word per thread: K (8 M + 4) bytes.
+__host__ __device__ constexpr size_t pw_pre_slot_bytes(int M, int K) { return (size_t)K * (8 * (size_t)M + 4); }
+static_assert(pw_pre_slot_bytes(10, 256) == 21504 && pw_pre_slot_bytes(18, 256) == 37888 &&
+              pw_pre_slot_bytes(20, 512) == 83968, "the shipped shapes' records");
+// the meta word: pw_canon's flag (the residue is 2^N', its limbs 0), the sign flag and the pending
+// exponent P < 2 N' < 2^12
+__host__ __device__ __forceinline__ u32 pw_pre_pack(int flag, int sign, unsigned P)
+{
+    return (u32)(flag & 1) << 13 | (u32)(sign & 1) << 12 | (P & 4095u);
+}
+__host__ __device__ __forceinline__ void pw_pre_unpack(u32 w, int &flag, int &sign, unsigned &P)
+{
+    flag = (int)(w >> 13) & 1;
+    sign = (int)(w >> 12) & 1;
+    P = w & 4095u;
+}
+static_assert(2 * 64 * 20 <= 4096, "pending exponents fit the meta word's 12 bits");
+
 // The end of a slot's inner product or square, from the pointwise results 2^Pz (-1)^Sz (Z, Tz): the
 // inverse transform with 2^-lk (division by K) and theta^-t, then the signed coefficients c_t into
 // X (limb-major, M rows) and their signs (+ limb M) into TT; stamps 5 and 6, ends with a barrier
@@ -1038,7 +1059,10 @@ __device__ __forceinline__ void pw_slot_tail(u64 (&Z)[M], int Tz, int Sz, unsign
 // loadB(Lb, Tb): when given (the tight form), operand B's pieces are loaded only after A's
 // forward transform, so the two operands' raw and formed pieces are never live together (the
 // kernel's register peak at 128 VGPRs; B's load latency is hidden by the CU's other workgroup)
-template <int M, int LK, typename LoadB = int>
+// PRE (k_pwsp): operand B is already weighted, transformed and canonical -- loadB(Lb, Tb) fetches
+// its cache record, the limbs into Lb and the meta word (pw_pre_pack) into Tb, after A's forward
+// transform and pw_canon; B's weight, transform and pw_canon are skipped
+template <int M, int LK, bool PRE = false, typename LoadB = int>
 __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[M], int Tb, u64 *X, u32 *Xw, int *TT,
                                                 int t, unsigned long long *stamp, LoadB loadB = 0)
 {
@@ -1050,25 +1074,39 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
     // again at l = 4096 (pw_launder): kept live from here to the un-weighting they took VGPRs that
     // kernel spilled (144 -> 96 B per lane, C4 pointwise 35.8 -> 34.9 ms)
     const bool half = (W2 & 1) && (t & 1);
-    unsigned Pa = pw_weight_exp<M, LK>(t), Pb = late_b ? 0u : Pa;
+    unsigned Pa = pw_weight_exp<M, LK>(t), Pb = late_b || PRE ? 0u : Pa;
     if (half) {
         pw_sqrt2<M>(La, Ta);
-        if (!late_b) pw_sqrt2<M>(Lb, Tb);
+        if (!late_b && !PRE) pw_sqrt2<M>(Lb, Tb);
     }
     pw_stamp(stamp, t, 1);
     pw_transform<M, LK, 0>(La, Ta, Sa, Pa, Xw, TT, W2, t);
     pw_stamp(stamp, t, 2);
-    if constexpr (late_b) {
-        loadB(Lb, Tb);
-        const int tb = pw_launder(t);
-        Pb = pw_weight_exp<M, LK>(tb);
-        if ((W2 & 1) && (tb & 1)) pw_sqrt2<M>(Lb, Tb);
+    int cb = 0;
+    if constexpr (!PRE) {
+        if constexpr (late_b) {
+            loadB(Lb, Tb);
+            const int tb = pw_launder(t);
+            Pb = pw_weight_exp<M, LK>(tb);
+            if ((W2 & 1) && (tb & 1)) pw_sqrt2<M>(Lb, Tb);
+        }
+        pw_transform<M, LK, 0, late_b ? pw_fixb_late : pw_fixb_early>(Lb, Tb, Sb, Pb, Xw, TT, W2, t);
     }
-    pw_transform<M, LK, 0, late_b ? pw_fixb_late : pw_fixb_early>(Lb, Tb, Sb, Pb, Xw, TT, W2, t);
     pw_stamp(stamp, t, 3);
 
     // ---- inner products: 2^Pa xa * 2^Pb xb = 2^(Pa + Pb) (xa xb) ---------------------
-    const int ca = pw_canon<M>(La, Ta), cb = pw_canon<M>(Lb, Tb);
+    const int ca = pw_canon<M>(La, Ta);
+    if constexpr (PRE) {
+        // the record after A's pw_canon: its M limbs are not live across that (k_pwsp's register peak)
+        static_assert(!PRE || late_b, "the cached form loads its record here");
+        loadB(Lb, Tb);
+        pw_pre_unpack((u32)Tb, cb, Sb, Pb);
+        // the product's sign and exponent cross the digit products as one opaque word (as Sa, Sb,
+        // Pa, Pb the l = 4096 forms spilled a register)
+        Tb = pw_launder((int)pw_pre_pack(0, Sa ^ Sb, pw_mod(Pa + Pb, N2)));
+    } else {
+        cb = pw_canon<M>(Lb, Tb);
+    }
     u64 Z[M];
     int Tz, Sz = Sa ^ Sb;
     if constexpr (pw_kara<M>()) {
@@ -1088,6 +1126,7 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
         pw_mulmod<M>(Z, Tz, La, ca, Lb, cb);
     }
     unsigned Pz = pw_mod(Pa + Pb, N2);
+    if constexpr (PRE) pw_pre_unpack((u32)Tb, cb, Sz, Pz);   // (as packed above)
     pw_stamp(stamp, t, 4);
 
     pw_slot_tail<M, LK>(Z, Tz, Sz, Pz, X, Xw, TT, t, stamp);
@@ -1440,6 +1479,122 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         pw_slot_square<M, LK>(La, Ta, X, Xw, TT, t, stamp);
         pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
     }
+    if (stamp) {
+        __syncthreads();
+        if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();
+    }
+}
+
+// ---------------------------------------------------------------------------
+// multiplication by a precomputed operand: operand B's slots are cached after their inner forward
+// transform (k_pwsx, once), and k_pwsp multiplies A's slots by the cached records -- k_pwss without
+// B's loads from the row arrays, its weight, its forward transform and its pw_canon.
+// ---------------------------------------------------------------------------
+
+// the slot of block b: the plain order at FUSE 0, k_pwss's XCD-aware order in the fused forms
+template <int FUSE>
+__device__ __forceinline__ long pw_block_slot(long b, long nb)
+{
+    if constexpr (FUSE == 0) return b;
+    else return pw_fused_slot<FUSE>(b, nb);
+}
+
+// thread t's part of slot `slot`'s cache record: its M limbs into L, returns its meta word
+template <int M, int LK>
+__device__ __forceinline__ u32 pw_pre_load(u64 (&L)[M], const unsigned char *pre, long slot, int t)
+{
+    constexpr int K = 1 << LK;
+    // (row bases on the workgroup-uniform record address, the thread's index a 32-bit offset: one
+    // address register per lane for all the rows)
+    const u64 *rec = (const u64 *)(pre + (size_t)slot * pw_pre_slot_bytes(M, K));
+#pragma unroll
+    for (int j = 0; j < M; ++j) L[j] = (rec + j * K)[(unsigned)t];
+    return ((const u32 *)(rec + M * K))[(unsigned)t];
+}
+
+// operand B's pieces (Lb, Tb) of one slot into its cache record: pw_slot_product's treatment of B
+// -- the weight (and pw_sqrt2), one forward transform, pw_canon -- then the coalesced store
+template <int M, int LK>
+__device__ __forceinline__ void pw_slot_precomp(u64 (&Lb)[M], int Tb, u32 *Xw, int *TT, int t, unsigned char *pre,
+                                                long slot, unsigned long long *stamp)
+{
+    constexpr int K = 1 << LK;
+    constexpr unsigned W2 = pw_w2<M, LK>();
+    int Sb = 0;
+    unsigned Pb = pw_weight_exp<M, LK>(t);
+    if ((W2 & 1) && (t & 1)) pw_sqrt2<M>(Lb, Tb);
+    pw_stamp(stamp, t, 1);
+    pw_transform<M, LK, 0>(Lb, Tb, Sb, Pb, Xw, TT, W2, t);
+    pw_stamp(stamp, t, 2);
+    const int cb = pw_canon<M>(Lb, Tb);
+    u64 *rec = (u64 *)(pre + (size_t)slot * pw_pre_slot_bytes(M, K));
+#pragma unroll
+    for (int j = 0; j < M; ++j) rec[j * K + t] = Lb[j];
+    ((u32 *)(rec + M * K))[t] = pw_pre_pack(cb, Sb, Pb);
+    pw_stamp(stamp, t, 3);
+}
+
+// k_pwsx<M, LK, FUSE>: B[slot] -> cache record `slot`, one workgroup of K threads per slot, k_pwss's
+// loaders for B (FUSE 1 / 2: the row DIF's last level(s) on load, paid here once) and its slot
+// order; no product and no output stage.
+template <int M, int LK, int FUSE>
+__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<M, LK>()))) void k_pwsx(const u64 *digB, const u64 *cbB, const int *topB, int l, unsigned char *pre,
+                                                  unsigned long long *dbg)
+{
+    unsigned long long *stamp = dbg ? dbg + 8 * (size_t)blockIdx.x : nullptr;
+    if (stamp && threadIdx.x == 0) stamp[0] = __builtin_amdgcn_s_memtime();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int K = 1 << LK;
+    const int t = threadIdx.x;
+    const auto [X, Xw, TT, H] = pw_lds_carve<M, LK>(smem);
+    const int cbw = cb_words(l);
+    constexpr int CLP = pw_piece_limbs<M, LK>();
+    const long slot = pw_block_slot<FUSE>(blockIdx.x, gridDim.x);
+    u64 Lb[M];
+    int Tb = 0;
+    if (FUSE == 0) pw_load_piece<M, CLP>(Lb, Tb, digB + (size_t)slot * l, cbB + (size_t)slot * cbw, topB + slot, l, t);
+    else if (FUSE == 2) pw_load_quad_bfly<M, CLP, K, pw_a_infl>(Lb, Tb, digB, cbB, topB, slot & ~3L, (int)(slot & 3), l, cbw, t);
+    else pw_load_pair_bfly<M, CLP>(Lb, Tb, digB, cbB, topB, slot & ~1L, l, cbw, t, slot & 1);
+    pw_slot_precomp<M, LK>(Lb, Tb, Xw, TT, t, pre, slot, stamp);
+    (void)X;
+    (void)H;
+    if (stamp) {
+        __syncthreads();
+        if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();
+    }
+}
+
+// k_pwsp<M, LK, FUSE>: A[slot] * cached B[slot] mod 2^N + 1.  A as in k_pwss (its loaders, weight
+// and forward transform), B's record from the cache -- with A's pieces, or in the tight form after
+// A's transform, where k_pwss loads B -- then the same product, inverse and output: to A in place
+// (FUSE 0) or to C (FUSE 1, 2).  The cache is only read.
+template <int M, int LK, int FUSE>
+__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<M, LK>()))) void k_pwsp(u64 *digA, u64 *cbA, int *topA, const unsigned char *pre, int l, u64 *digC, u64 *cbC,
+                                                  int *topC, unsigned long long *dbg)
+{
+    unsigned long long *stamp = dbg ? dbg + 8 * (size_t)blockIdx.x : nullptr;
+    if (stamp && threadIdx.x == 0) stamp[0] = __builtin_amdgcn_s_memtime();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int K = 1 << LK;
+    const int t = threadIdx.x;
+    const auto [X, Xw, TT, H] = pw_lds_carve<M, LK>(smem);
+    const int cbw = cb_words(l);
+    constexpr int CLP = pw_piece_limbs<M, LK>();
+    const long slot = pw_block_slot<FUSE>(blockIdx.x, gridDim.x);
+    u64 La[M], Lb[M];
+    int Ta = 0, Tb = 0;
+    if (FUSE == 0) pw_load_piece<M, CLP>(La, Ta, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
+    else if (FUSE == 2) pw_load_quad_bfly<M, CLP, K, pw_a_infl>(La, Ta, digA, cbA, topA, slot & ~3L, (int)(slot & 3), l, cbw, t);
+    else pw_load_pair_bfly<M, CLP>(La, Ta, digA, cbA, topA, slot & ~1L, l, cbw, t, slot & 1);
+    // B's record is loaded after A's transform and pw_canon in every form, not only the tight one
+    // (pw_slot_product PRE): all M limbs of a record are live, where the upper limbs of k_pwss's
+    // raw pieces are one sign register, and held across A's transform or pw_canon they spilled
+    // (80-120 B per lane).  A's transform has barriers: every piece of A is read before the
+    // in-place output.
+    auto loadB = [&](u64 (&L)[M], int &T) { T = (int)pw_pre_load<M, LK>(L, pre, slot, pw_launder(t)); };
+    pw_slot_product<M, LK, true>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp, loadB);
+    if (FUSE == 0) pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
+    else pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
     if (stamp) {
         __syncthreads();
         if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();

@@ -67,6 +67,8 @@ struct Plan {
     int fuse_rows;      // row DIF levels that run inside the pointwise: 1 (slot pairs), 2 (slot quads), 0
     size_t off_digC, off_topC, off_cbC;
     bool sqr;           // squaring plan (make_plan_sqr): one operand, no B arrays in the layout
+    bool pre;           // multiply against a precomputed operand B (make_plan_pre): no B arrays in the layout
+                        // either, but two operands -- the pointwise reads B from the cache (plan_pre_bytes)
     // make_plan_mod: a product mod 2^(64 n1) + 1 as a length-2n negacyclic convolution (nega.hpp)
     bool nega;
     size_t off_nflags;  // k_nwrap's look-back flags, ticket counter and overflow word (behind off_flags:
@@ -332,11 +334,13 @@ static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned lo
 }
 
 // operand B's arrays (dig + top + cbb of make_plan_split) out of a plan's layout: everything
-// behind them moves down by their size
-static void plan_drop_b(Plan *p)
+// behind them moves down by their size.  sqr: a squaring plan; else a multiply against a
+// precomputed operand (Plan::pre)
+static void plan_drop_b(Plan *p, bool sqr = true)
 {
     const size_t b = (p->has_c ? p->off_digC : p->off_flags) - p->off_digB;
-    p->sqr = true;
+    p->sqr = sqr;
+    p->pre = !sqr;
     p->off_digB = p->off_topB = p->off_cbB = 0;
     if (p->has_c) {
         p->off_digC -= b;
@@ -355,6 +359,30 @@ static int make_plan_sqr(Plan *p, long n, unsigned long depth, unsigned long w)
     const int rc = make_plan(p, n, n, depth, w);
     if (rc) return rc;
     plan_drop_b(p);
+    return MPFFT_OK;
+}
+
+// Multiplication by a precomputed operand.  The cache of operand B for the multiply's plan P:
+// on nested plans one record per live slot, B after its inner forward transform
+// (pw_pre_record_bytes); on the other families the live slots of B's fully transformed row arrays
+// as those kernels read them, canonical: the limbs, then the carry limbs.
+static size_t plan_pre_dig_bytes(const Plan &P) { return (size_t)P.trunc * P.l * 8; }
+static size_t plan_pre_bytes(const Plan &P)
+{
+    if (pw_family(P) == PWF_NESTED) {
+        const int lk = pwss_lk_of(P.l);
+        return (size_t)P.trunc * pw_pre_record_bytes(pw_inner_limbs(P.l, lk), 1 << lk);
+    }
+    return plan_pre_dig_bytes(P) + align_up((size_t)P.trunc * 4, 256);
+}
+
+// The plan of a multiply against the cache: the multiply's plan for (n1, n2, depth, w) with
+// operand B's arrays taken out of the layout (operand 0 alone runs the forward stages).
+static int make_plan_pre(Plan *p, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    const int rc = make_plan(p, n1, n2, depth, w);
+    if (rc) return rc;
+    plan_drop_b(p, false);
     return MPFFT_OK;
 }
 
