@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 5
+#define MPFFT_VERSION 6
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -120,7 +120,7 @@ int mpfft_sqr_stage_kernels(long n, unsigned long depth, unsigned long w, char *
  * efficient moduli lie a factor 2 apart (B ~ n^2 w); for B a power of two (Fermat numbers) the
  * pieces are N/4 bits, not N/2, and the slot count equals that of the multiply-and-fold route
  * (the reference's low-limb CRT trick, which would close that gap, is not implemented).
- * Not covered: mod 2^B - 1, the sqrt2 front end, the sharded / multi-GPU entries and
+ * Not covered: the sqrt2 front end, the sharded / multi-GPU entries and
  * mpfft_set_devices routing -- these always run on the calling thread's device. */
 int mpfft_mulmod_check_params(long L, unsigned long depth, unsigned long w);
 int mpfft_mulmod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w);
@@ -206,6 +206,72 @@ typedef struct mpfft_pre mpfft_pre;
 int mpfft_precomp_create(mpfft_pre **out, const uint64_t *i2, long n2, long n1, unsigned long depth, unsigned long w);
 int mpfft_mul_precomp_ex(uint64_t *r, const uint64_t *i1, long n1, const mpfft_pre *pre);
 void mpfft_precomp_destroy(mpfft_pre *pre);
+
+/* ---- products mod 2^B - 1 (MPFFT_VERSION 6): r = a b mod M, M = 2^B - 1, B = 64 L, as a
+ * length-2n cyclic convolution mod 2^N + 1 (n = 2^depth, N = n w) of bits1 = B / 2n bit pieces --
+ * what the untruncated transform computes as it stands (2^B == 1: GMP's mpn_mulmod_bnm1, the
+ * wraparound trick): no weight, no sqrt2, the first column pass splits the operands, and the
+ * coefficients are non-negative.  Half the slots of the full product at the same coefficient size
+ * and L limbs over the bus instead of 2 L; with the residue mod 2^B + 1 it gives a 2B-bit product
+ * by CRT, and where part of a product is already known (Newton and Barrett steps) it recovers the
+ * rest.
+ * Operands: L limbs each, any value 0 <= a < 2^B (all-ones is accepted; it is 0 mod M).  Result:
+ * L limbs, fully reduced, 0 <= r < M -- all-ones is never returned.  r may not overlap a or b;
+ * d_r may be the next call's operand.
+ * Valid (L, depth, w): 2 <= depth <= 30, 64 | N, 2n | 64 L (MPFFT_EINVAL otherwise);
+ * 2 bits1 + depth + 1 <= N, so that c_k <= 2n (2^bits1 - 1)^2 < 2^N (MPFFT_ETOOBIG) -- one bit
+ * more room than mod 2^B + 1; N / 64 <= 4096 (MPFFT_EUNSUPPORTED).  mpfft_mulmodm1_next_size gives
+ * an efficient L.
+ * kind: MPFFT_M1_MUL, MPFFT_M1_SQR (one operand split and transformed once, no B arrays, k_pwsq on
+ * the nested plans) or MPFFT_M1_PRE (the multiply against a cached operand: no B arrays either).
+ * Limits: the efficient sizes lie a factor 2 apart (B ~ n^2 w with power-of-two w: nothing is
+ * truncated); B a power of two has bits1 = N/4.
+ * Not covered: the sqrt2 front end, the sharded / multi-GPU entries and mpfft_set_devices
+ * routing -- these always run on the calling thread's device. */
+#define MPFFT_M1_MUL 0
+#define MPFFT_M1_SQR 1
+#define MPFFT_M1_PRE 2
+int mpfft_mulmodm1_check_params(long L, unsigned long depth, unsigned long w);
+/* Host pointers, L limbs each; the operands are not inspected (every value is valid). */
+int mpfft_mulmodm1_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w);
+int mpfft_sqrmodm1_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w);
+/* Device-resident, queued on `stream` and not synchronised; d_ws holds
+ * mpfft_mulmodm1_workspace_bytes(L, depth, w, kind) bytes and need not be cleared. */
+int mpfft_mulmodm1_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                          unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+int mpfft_sqrmodm1_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                          void *d_ws, size_t ws_bytes, void *stream);
+size_t mpfft_mulmodm1_workspace_bytes(long L, unsigned long depth, unsigned long w, int kind);   /* 0 on invalid parameters */
+/* out[10] as mpfft_plan_info: j1 = j2 = trunc = 2n, bits1 = 64 L / 2n. */
+int mpfft_mulmodm1_plan_info(long L, unsigned long depth, unsigned long w, long *out);
+/* out[8] as mpfft_workspace_layout (MPFFT_M1_SQR, MPFFT_M1_PRE: entries 3..5 are 0). */
+int mpfft_mulmodm1_workspace_layout(long L, unsigned long depth, unsigned long w, int kind, size_t *out);
+/* One stage on the workspace (tests; kind MPFFT_M1_MUL or MPFFT_M1_SQR).  MPFFT_STAGE_FWD_COLUMNS:
+ * the split and the column transform; MPFFT_STAGE_SCALE: the plain scaling by 2^-(depth+1),
+ * canonical (also where the whole product fuses it into the last inverse column pass);
+ * MPFFT_STAGE_COMBINE: the cyclic combine of the canonical coefficients into d_r (L limbs; it
+ * clears its own flags); the others are the multiply's.  MPFFT_STAGE_DRIVEN and
+ * MPFFT_STAGE_FOLD_COMBINE return MPFFT_EINVAL. */
+int mpfft_mulmodm1_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                         unsigned long depth, unsigned long w, int kind, void *d_ws, size_t ws_bytes, void *stream);
+/* As mpfft_stage_kernels; the fwd_columns field names the pass that splits, the combine field
+ * "k_combine1 + k_cwrap + k_cfix (cyclic)". */
+int mpfft_mulmodm1_stage_kernels(long L, unsigned long depth, unsigned long w, int kind, char *buf, size_t len);
+/* As mpfft_mulmod_choose / mpfft_mulmod_next_size, for the cyclic bound. */
+int mpfft_mulmodm1_choose(long L, unsigned long *depth, unsigned long *w);
+int mpfft_mulmodm1_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w);
+/* Cached operand (device level; no host handle): mpfft_mulmodm1_precomp_device runs d_b's forward
+ * stages once into d_pre (mpfft_mulmodm1_precomp_bytes; d_ws holds the MPFFT_M1_MUL workspace), and
+ * mpfft_mulmodm1_mul_precomp_device computes d_r = d_a (the cached b) mod M on the MPFFT_M1_PRE
+ * workspace, limb-equal to mpfft_mulmodm1_device.  The cache follows the rules of mpfft_precomp_*:
+ * bound to (L, depth, w), to the MPFFT_POINTWISE selection and to the library version, only read
+ * by a multiply (streams may share it); a workspace or cache that is too small returns
+ * MPFFT_ENOMEM. */
+size_t mpfft_mulmodm1_precomp_bytes(long L, unsigned long depth, unsigned long w);   /* 0 on invalid parameters */
+int mpfft_mulmodm1_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t *d_b, long L, unsigned long depth,
+                                  unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+int mpfft_mulmodm1_mul_precomp_device(uint64_t *d_r, const uint64_t *d_a, const void *d_pre, size_t pre_bytes, long L,
+                                      unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity

@@ -233,6 +233,39 @@ def lib():
             h.mpfft_mul_precomp_ex.restype = ctypes.c_int
             h.mpfft_precomp_destroy.argtypes = [_vp]
             h.mpfft_precomp_destroy.restype = None
+        if hasattr(h, "mpfft_mulmodm1_ex"):   # MPFFT_VERSION 6 (older libraries in A/B runs lack them)
+            _ulp = ctypes.POINTER(ctypes.c_ulong)
+            _sz = ctypes.c_size_t
+            h.mpfft_mulmodm1_check_params.argtypes = [_L, _UL, _UL]
+            h.mpfft_mulmodm1_check_params.restype = ctypes.c_int
+            h.mpfft_mulmodm1_ex.argtypes = [_u64p, _u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_mulmodm1_ex.restype = ctypes.c_int
+            h.mpfft_sqrmodm1_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_sqrmodm1_ex.restype = ctypes.c_int
+            h.mpfft_mulmodm1_device.argtypes = [_vp, _vp, _vp, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_mulmodm1_device.restype = ctypes.c_int
+            h.mpfft_sqrmodm1_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_sqrmodm1_device.restype = ctypes.c_int
+            h.mpfft_mulmodm1_workspace_bytes.argtypes = [_L, _UL, _UL, ctypes.c_int]
+            h.mpfft_mulmodm1_workspace_bytes.restype = _sz
+            h.mpfft_mulmodm1_plan_info.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
+            h.mpfft_mulmodm1_plan_info.restype = ctypes.c_int
+            h.mpfft_mulmodm1_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.POINTER(_sz)]
+            h.mpfft_mulmodm1_workspace_layout.restype = ctypes.c_int
+            h.mpfft_mulmodm1_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _UL, _UL, ctypes.c_int, _vp, _sz, _vp]
+            h.mpfft_mulmodm1_stage.restype = ctypes.c_int
+            h.mpfft_mulmodm1_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.c_char_p, _sz]
+            h.mpfft_mulmodm1_stage_kernels.restype = ctypes.c_int
+            h.mpfft_mulmodm1_choose.argtypes = [_L, _ulp, _ulp]
+            h.mpfft_mulmodm1_choose.restype = ctypes.c_int
+            h.mpfft_mulmodm1_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
+            h.mpfft_mulmodm1_next_size.restype = ctypes.c_int
+            h.mpfft_mulmodm1_precomp_bytes.argtypes = [_L, _UL, _UL]
+            h.mpfft_mulmodm1_precomp_bytes.restype = _sz
+            h.mpfft_mulmodm1_precomp_device.argtypes = [_vp, _sz, _vp, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_mulmodm1_precomp_device.restype = ctypes.c_int
+            h.mpfft_mulmodm1_mul_precomp_device.argtypes = [_vp, _vp, _vp, _sz, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_mulmodm1_mul_precomp_device.restype = ctypes.c_int
         _lib = h
     return _lib
 
@@ -797,6 +830,166 @@ def mulmod_next_size(min_L):
     if rc:
         raise MpfftError(rc, f"mulmod_next_size({min_L})")
     return int(L.value), int(d.value), int(w.value)
+
+
+# ---- products mod 2^B - 1, B = 64 L (mpfft_mulmodm1_*, include/mpfft.h): operands and result are
+# L limbs; any operand value is valid, the result is fully reduced (never all-ones) ----
+M1_MUL, M1_SQR, M1_PRE = 0, 1, 2   # plan kinds: multiply, square, multiply against a cached operand
+
+
+def mulmodm1_check_params(L, depth, w):
+    return lib().mpfft_mulmodm1_check_params(L, depth, w)
+
+
+def mulmodm1(a, b, depth, w):
+    """a b mod 2^(64 L) - 1 for L-limb a, b: a new uint64 array of L limbs, fully reduced."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if len(a) != len(b) or len(a) < 1:
+        raise ValueError("operands are L limbs each")
+    L = len(a)
+    r = np.zeros(L, dtype=np.uint64)
+    rc = lib().mpfft_mulmodm1_ex(_p(r), _p(a), _p(b), L, depth, w)
+    if rc:
+        raise MpfftError(rc, f"mulmodm1(L={L}, depth={depth}, w={w})")
+    return r
+
+
+def sqrmodm1(a, depth, w):
+    """a^2 mod 2^(64 L) - 1 (one forward transform)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if len(a) < 1:
+        raise ValueError("the operand is L limbs")
+    L = len(a)
+    r = np.zeros(L, dtype=np.uint64)
+    rc = lib().mpfft_sqrmodm1_ex(_p(r), _p(a), L, depth, w)
+    if rc:
+        raise MpfftError(rc, f"sqrmodm1(L={L}, depth={depth}, w={w})")
+    return r
+
+
+def mulmodm1_workspace_bytes(L, depth, w, kind=M1_MUL):
+    return int(lib().mpfft_mulmodm1_workspace_bytes(L, depth, w, int(kind)))
+
+
+def alloc_workspace_mulmodm1(L, depth, w, kind=M1_MUL, device="cuda"):
+    import torch
+    nb = mulmodm1_workspace_bytes(L, depth, w, kind)
+    if nb == 0:
+        raise MpfftError(mulmodm1_check_params(L, depth, w) or 1, "mulmodm1 workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def mulmodm1_device(d_r, d_a, d_b, L, depth, w, ws, stream=None):
+    """d_r[:L] = d_a d_b mod 2^(64 L) - 1 on the GPU; queued on `stream`, not synchronised.
+    d_r may not overlap an operand (it may be the next call's)."""
+    rc = lib().mpfft_mulmodm1_device(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws),
+                                     ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmodm1_device")
+
+
+def sqrmodm1_device(d_r, d_a, L, depth, w, ws, stream=None):
+    rc = lib().mpfft_sqrmodm1_device(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws),
+                                     ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_sqrmodm1_device")
+
+
+def mulmodm1_plan_info(L, depth, w):
+    out = (ctypes.c_long * 10)()
+    rc = lib().mpfft_mulmodm1_plan_info(L, depth, w, out)
+    if rc:
+        raise MpfftError(rc, f"mulmodm1 plan(L={L}, depth={depth}, w={w})")
+    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
+    return dict(zip(keys, list(out)))
+
+
+def mulmodm1_workspace_layout(L, depth, w, kind=M1_MUL):
+    out = (ctypes.c_size_t * 8)()
+    rc = lib().mpfft_mulmodm1_workspace_layout(L, depth, w, int(kind), out)
+    if rc:
+        raise MpfftError(rc, "mulmodm1_workspace_layout")
+    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
+    return dict(zip(keys, list(out)))
+
+
+def mulmodm1_workspace_views(ws, L, depth, w, kind=M1_MUL):
+    """(digA, topA, cbA) views into a mulmodm1 workspace tensor (slot-major): limbs (slots, l) int64,
+    carry limbs int32, carry masks (slots, cbw) int64."""
+    import torch
+    P = mulmodm1_plan_info(L, depth, w)
+    lay = mulmodm1_workspace_layout(L, depth, w, kind)
+    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
+    u8 = ws.view(torch.uint8)
+    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
+    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
+    cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
+    return dig, top, cb
+
+
+def mulmodm1_stage(which, d_a, d_b, d_r, L, depth, w, ws, kind=M1_MUL, stream=None):
+    rc = lib().mpfft_mulmodm1_stage(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, int(kind), _ptr(ws),
+                                    ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_mulmodm1_stage({which})")
+
+
+def mulmodm1_stage_kernels(L, depth, w, kind=M1_MUL):
+    """dict stage -> the kernel a product mod 2^(64 L) - 1 launches for it"""
+    buf = ctypes.create_string_buffer(512)
+    rc = lib().mpfft_mulmodm1_stage_kernels(L, depth, w, int(kind), buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmodm1_stage_kernels")
+    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+
+
+def mulmodm1_choose(L):
+    """(depth, w) of least predicted time that are valid for this L."""
+    d, w = ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_mulmodm1_choose(L, ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"mulmodm1_choose(L={L})")
+    return int(d.value), int(w.value)
+
+
+def mulmodm1_next_size(min_L):
+    """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
+    L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_mulmodm1_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"mulmodm1_next_size({min_L})")
+    return int(L.value), int(d.value), int(w.value)
+
+
+def mulmodm1_precomp_bytes(L, depth, w):
+    return int(lib().mpfft_mulmodm1_precomp_bytes(L, depth, w))
+
+
+def alloc_precomp_mulmodm1(L, depth, w, device="cuda"):
+    import torch
+    nb = mulmodm1_precomp_bytes(L, depth, w)
+    if nb == 0:
+        raise MpfftError(mulmodm1_check_params(L, depth, w) or 1, "mulmodm1 precomp")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def mulmodm1_precomp_device(pre, d_b, L, depth, w, ws, stream=None):
+    """The cache of operand d_b (L limbs) for products mod 2^(64 L) - 1 against it; ws: the
+    multiply's workspace (kind M1_MUL)."""
+    rc = lib().mpfft_mulmodm1_precomp_device(_ptr(pre), pre.numel() * pre.element_size(), _ptr(d_b), L, depth, w,
+                                             _ptr(ws), ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmodm1_precomp_device")
+
+
+def mulmodm1_mul_precomp_device(d_r, d_a, pre, L, depth, w, ws, stream=None):
+    """d_r[:L] = d_a (the cached operand) mod 2^(64 L) - 1; ws: the workspace of kind M1_PRE; pre is
+    only read."""
+    rc = lib().mpfft_mulmodm1_mul_precomp_device(_ptr(d_r), _ptr(d_a), _ptr(pre), pre.numel() * pre.element_size(), L,
+                                                 depth, w, _ptr(ws), ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmodm1_mul_precomp_device")
 
 
 # ---- sharded (multi-GPU) stages: see sharded.py ------------------------------

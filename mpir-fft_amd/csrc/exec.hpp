@@ -1178,4 +1178,31 @@ struct Exec {
         if ((rc = launch(k_nwrap<NEGA_V>, dim3((unsigned)a.nblk), dim3(256), 0, a, r, st))) return rc;
         return launch(k_nfix, dim3(1), dim3(1024), 0, r, (long)P.n1, (const u32 *)st, a.nblk);
     }
+
+    // ---- the cyclic top level (cyc.hpp) on a make_plan_cyc plan ---------------------------
+    // words of both combine flag regions from comb_flags() on (the first forward column pass clears them)
+    static long cyc_flag_words(const Plan &P) { return (long)((P.off_nflags - P.off_flags) / 4) + cyc_blocks(P.n1) + CYC_XW; }
+
+    // the plain scaling by 2^-(depth+1), canonical, whatever the plan fuses (the stage entry)
+    int cscale() { return scale_rows(0, P.NR, 2 * P.N - (u64)(P.depth + 1)); }
+
+    // cyclic combine: k_combine1 into the scratch, k_cwrap, k_cfix; r: L limbs
+    int ccombine(u64 *r, unsigned char *ws)
+    {
+        u64 *T = (u64 *)(ws + P.off_nscr);
+        u32 *st = (u32 *)(ws + P.off_nflags);
+        const bool cleared = zflags == comb_flags(ws);
+        int rc = combine_single(T, ws);
+        if (rc) return rc;
+        CycCombArgs a;
+        memset(&a, 0, sizeof(a));
+        a.T = T;
+        a.TL = P.total;
+        a.L = P.n1;
+        a.nT = (int)((P.total + P.n1 - 1) / P.n1);
+        a.nblk = cyc_blocks(P.n1);
+        if (!cleared) HIPCHK(hipMemsetAsync(st, 0, (size_t)(a.nblk + CYC_XW) * 4, s));
+        if ((rc = launch(k_cwrap<CYC_V>, dim3((unsigned)a.nblk), dim3(256), 0, a, r, st))) return rc;
+        return launch(k_cfix, dim3(1), dim3(1024), 0, r, (long)P.n1, (const u32 *)st, a.nblk);
+    }
 };

@@ -34,6 +34,7 @@
 #include "combine.hpp"
 #include "fold.hpp"
 #include "nega.hpp"
+#include "cyc.hpp"
 #include "wdispatch.hpp"
 #include "bdispatch.hpp"
 #include "pdispatch.hpp"
@@ -200,6 +201,9 @@ static int fwd_op(const Plan &P) { return P.sqr || P.pre ? 0 : -1; }
 // d_i2 alike: one split, one forward column and row transform (that pass still clears the
 // combine flags), the pointwise in squaring mode (k_pwsq, or the other families with B = A),
 // then the multiply's inverse, scaling and combine unchanged.
+// A cyclic plan (make_plan_cyc, cyc.hpp: the product mod 2^B - 1, d_i1, d_i2 and d_r of L limbs) runs
+// the same stages untruncated -- the split pass's zero bounds come out as "nothing pruned" -- and
+// ends in the cyclic combine; its squares and cached operands work as the multiply's.
 // d_pre: the cache of a precomputed operand B (plan_pre_bytes).  On a Plan::pre plan (make_plan_pre)
 // the product is d_i1 times the cached operand: operand 0's forward stages, the pointwise against
 // the cache, the rest unchanged.  pre_make (the multiply's own plan and workspace): operand B's
@@ -214,7 +218,7 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
     X.use_pre(d_pre);
     X.pre_make = pre_make;
     X.zflags = X.comb_flags(ws);
-    X.zflags_n = X.comb_flag_words(P, P.total);
+    X.zflags_n = P.cyc ? Exec::cyc_flag_words(P) : X.comb_flag_words(P, P.total);   // cyclic: k_cwrap's behind them
     X.drive_single();
     X.fuse_row_last = true;  // last row level inside the pointwise (nested negacyclic sizes)
     ProfCall pc;
@@ -254,7 +258,7 @@ static int run_all(const Plan &P, u64 *d_r, const u64 *d_i1, const u64 *d_i2, un
     pc.mark(5, s);
     if ((rc = X.scale())) return rc;
     pc.mark(6, s);
-    rc = X.fold ? X.combine_fold(d_r, ws, X.dbl_lo, X.dbl_hi) : X.combine_single(d_r, ws);
+    rc = P.cyc ? X.ccombine(d_r, ws) : X.fold ? X.combine_fold(d_r, ws, X.dbl_lo, X.dbl_hi) : X.combine_single(d_r, ws);
     pc.mark(7, s);
     return rc;
 }
@@ -362,6 +366,10 @@ static std::string stage_kernel_names(const Plan &P)
         snprintf(fwdc, sizeof fwdc, "%s (split: k_rpass<%d,%d,0,2>)", pass, fg, fp);
     else
         snprintf(fwdc, sizeof fwdc, "%s", pass);
+    if (P.cyc) {   // the cyclic top level (cyc.hpp): the first column pass splits, the fold is its own
+        if (!(fn > 0)) snprintf(fwdc, sizeof fwdc, "%s (split)", pass);
+        comb = "k_combine1 + k_cwrap + k_cfix (cyclic)";
+    }
     if (P.nega) {   // the negacyclic top level's own launches (nega.hpp)
         Exec X(P, nullptr);
         char unw[64];
@@ -525,9 +533,11 @@ const char *mpfft_strerror(int code)
     switch (code) {
     case MPFFT_OK: return "ok";
     case MPFFT_EINVAL: return "invalid parameters (need n1,n2 >= 1, 2 <= depth <= 30, n*w % 64 == 0)"
-                              "; mod 2^B+1: L >= 1, 2^(depth+1) | 64 L, operands fully reduced";
+                              "; mod 2^B+1: L >= 1, 2^(depth+1) | 64 L, operands fully reduced"
+                              "; mod 2^B-1: L >= 1, 2^(depth+1) | 64 L, r overlapping no operand";
     case MPFFT_ETOOBIG: return "operands too large for the convolution: need j1 + j2 - 1 <= 2^(depth+1)"
-                               "; mod 2^B+1: 2 bits1 + depth + 2 <= n*w, bits1 = 64 L / 2^(depth+1)";
+                               "; mod 2^B+1: 2 bits1 + depth + 2 <= n*w, bits1 = 64 L / 2^(depth+1)"
+                               "; mod 2^B-1: 2 bits1 + depth + 1 <= n*w";
     case MPFFT_EUNSUPPORTED: return "coefficient size n*w/64 > 4096 limbs is not supported";
     case MPFFT_ENOMEM: return "device allocation failed";
     case MPFFT_EHIP: return hipGetErrorString(last_hip_error);
@@ -1289,6 +1299,201 @@ int mpfft_mulmod_next_size(long min_L, long *L, unsigned long *depth, unsigned l
 {
     if (min_L < 1) return MPFFT_EINVAL;
     return mulmod_pick(0, min_L, L, depth, w);
+}
+
+// ---- products mod 2^B - 1 (cyc.hpp, make_plan_cyc): run_all on a cyclic plan.  Out of scope as for
+// the squares: the sqrt2 front end, the sharded and multi-GPU entries, mpfft_set_devices routing;
+// the cached operand has no host handle. ---------------------------------------------------------
+int mpfft_mulmodm1_check_params(long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_cyc(&P, L, depth, w, CYC_MUL);
+}
+
+size_t mpfft_mulmodm1_workspace_bytes(long L, unsigned long depth, unsigned long w, int kind)
+{
+    Plan P;
+    if (make_plan_cyc(&P, L, depth, w, kind)) return 0;
+    return P.bytes;
+}
+
+int mpfft_mulmodm1_plan_info(long L, unsigned long depth, unsigned long w, long *out)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
+    if (rc) return rc;
+    plan_info_out(P, out);
+    return MPFFT_OK;
+}
+
+int mpfft_mulmodm1_workspace_layout(long L, unsigned long depth, unsigned long w, int kind, size_t *out)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, kind);
+    if (rc) return rc;
+    layout_out(P, out);
+    return MPFFT_OK;
+}
+
+// [p, p + n) and [q, q + m) limbs share an address
+static bool limbs_overlap(const uint64_t *p, long n, const uint64_t *q, long m) { return p < q + m && q < p + n; }
+
+int mpfft_mulmodm1_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                          unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (limbs_overlap(d_r, L, d_a, L) || limbs_overlap(d_r, L, d_b, L)) return MPFFT_EINVAL;
+    (void)hipGetLastError();
+    return run_all(P, d_r, d_a, d_b, (unsigned char *)d_ws, (hipStream_t)stream);
+}
+
+int mpfft_sqrmodm1_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                          void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_SQR);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (limbs_overlap(d_r, L, d_a, L)) return MPFFT_EINVAL;
+    (void)hipGetLastError();
+    return run_all(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream);
+}
+
+int mpfft_mulmodm1_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                         unsigned long depth, unsigned long w, int kind, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    if (kind != CYC_MUL && kind != CYC_SQR) return MPFFT_EINVAL;
+    int rc = make_plan_cyc(&P, L, depth, w, kind);
+    if (rc) return rc;
+    if ((stage & MPFFT_STAGE_DRIVEN) || stage == MPFFT_STAGE_FOLD_COMBINE) return MPFFT_EINVAL;
+    if (stage != MPFFT_STAGE_SCALE && stage != MPFFT_STAGE_COMBINE)   // the multiply's, Tr = NR (the columns split)
+        return single_stage(P, stage, d_a, kind == CYC_SQR ? d_a : d_b, d_r, d_ws, ws_bytes, stream);
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    Exec X(P, (hipStream_t)stream);
+    X.single((unsigned char *)d_ws);
+    if (stage == MPFFT_STAGE_SCALE) return X.cscale();
+    return X.ccombine(d_r, (unsigned char *)d_ws);
+}
+
+int mpfft_mulmodm1_stage_kernels(long L, unsigned long depth, unsigned long w, int kind, char *buf, size_t len)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, kind);
+    if (rc) return rc;
+    return copy_out(stage_kernel_names(P), buf, len);
+}
+
+// host operands on the calling thread's device (as mulmod_host): io holds a, b and r, L limbs each
+static int cyc_host(const Plan &P, uint64_t *r, const uint64_t *a, const uint64_t *b)
+{
+    const long L = P.n1;
+    int rc, dev = 0;
+    DevCtx *Cp;
+    if ((rc = host_ctx(&Cp, &dev))) return rc;
+    DevCtx &C = *Cp;
+    std::lock_guard<std::mutex> lk(C.mu);
+    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
+    const size_t nb = (size_t)L * 8;
+    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, 3 * nb))) return rc;
+    u64 *d_a = C.io, *d_b = P.sqr ? d_a : d_a + L, *d_r = C.io + 2 * L;
+    HIPCHK(hipMemcpyAsync(d_a, a, nb, hipMemcpyHostToDevice, C.stream));
+    if (!P.sqr) HIPCHK(hipMemcpyAsync(d_b, b, nb, hipMemcpyHostToDevice, C.stream));
+    if ((rc = run_all(P, d_r, d_a, d_b, C.ws, C.stream))) return rc;
+    HIPCHK(hipMemcpyAsync(r, d_r, nb, hipMemcpyDeviceToHost, C.stream));
+    HIPCHK(hipStreamSynchronize(C.stream));
+    g_last_ngpus = 1;
+    return MPFFT_OK;
+}
+
+int mpfft_mulmodm1_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
+    if (rc) return rc;
+    return cyc_host(P, r, a, b);
+}
+
+int mpfft_sqrmodm1_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_SQR);
+    if (rc) return rc;
+    return cyc_host(P, r, a, a);
+}
+
+size_t mpfft_mulmodm1_precomp_bytes(long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan_cyc(&P, L, depth, w, CYC_MUL)) return 0;
+    return plan_pre_bytes(P);
+}
+
+int mpfft_mulmodm1_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t *d_b, long L, unsigned long depth,
+                                  unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    return run_all(P, nullptr, nullptr, d_b, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre, true);
+}
+
+int mpfft_mulmodm1_mul_precomp_device(uint64_t *d_r, const uint64_t *d_a, const void *d_pre, size_t pre_bytes, long L,
+                                      unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, CYC_PRE);
+    if (rc) return rc;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
+    if (limbs_overlap(d_r, L, d_a, L)) return MPFFT_EINVAL;
+    (void)hipGetLastError();
+    return run_all(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre);
+}
+
+// as mulmod_pick, on the cyclic plans
+static int cyc_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w)
+{
+    double best = -1.0;
+    for (unsigned long d = 2; d <= 24; ++d)
+        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
+            const unsigned long long N = (1ull << d) * wv;
+            if (N % 64) continue;
+            if (N / 64 > 4096) break;
+            const long g = std::max<long>(1, (2L << d) / 64);
+            const long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
+            Plan P;
+            if (make_plan_cyc(&P, Lc, d, wv, CYC_MUL)) continue;
+            const double c = choose_cost(P);
+            if (best < 0 || c < best) {
+                best = c;
+                *L = Lc;
+                *depth = d;
+                *w = wv;
+            }
+        }
+    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+}
+
+int mpfft_mulmodm1_choose(long L, unsigned long *depth, unsigned long *w)
+{
+    long Lc = 0;
+    if (L < 1) return MPFFT_EINVAL;
+    return cyc_pick(L, 0, &Lc, depth, w);
+}
+
+int mpfft_mulmodm1_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w)
+{
+    if (min_L < 1) return MPFFT_EINVAL;
+    return cyc_pick(0, min_L, L, depth, w);
 }
 
 // release the calling device's cached workspace (the next call re-allocates)

@@ -74,6 +74,9 @@ struct Plan {
     size_t off_nflags;  // k_nwrap's look-back flags, ticket counter and overflow word (behind off_flags:
                         // the weight launch clears both in one range)
     size_t off_nscr;    // the unsigned sum of the canonical coefficients (k_combine1's output), `total` limbs
+    // make_plan_cyc: a product mod 2^(64 n1) - 1 as a length-2n cyclic convolution (cyc.hpp); off_nflags
+    // and off_nscr hold k_cwrap's flags and the scratch sum as they do k_nwrap's on a negacyclic plan
+    bool cyc;
 };
 
 static int ilog2(long v) { int d = 0; while ((1L << d) < v) ++d; return d; }
@@ -423,6 +426,57 @@ static int make_plan_mod(Plan *p, long L, unsigned long depth, unsigned long w, 
     size_t o = p->off_flags;
     o += align_up((size_t)(p->total / 256 + 8) * 4, 256);
     p->off_nflags = o; o += align_up((size_t)(nega_blocks(L) + 2) * 4, 256);
+    p->off_meta = o; o += align_up((size_t)p->slots * 4, 256);
+    p->off_nscr = o; o += align_up((size_t)p->total * 8, 256);
+    p->bytes = o;
+    return MPFFT_OK;
+}
+
+// Cyclic plan (cyc.hpp): a b mod 2^B - 1, B = 64 L, as the length-2n cyclic convolution of
+// bits1 = B / 2n bit pieces -- what the untruncated transform computes as it stands: no weight, the
+// first column pass splits the operands, the multiply's scaling at Tr = NR (fused on the wave
+// plans).  Kernel families and split as make_plan_mod's.  The coefficients are non-negative,
+// c_k <= 2n (2^bits1 - 1)^2, so 2 bits1 + depth + 1 <= N keeps them below 2^N.
+// kind: the multiply, the square (no B arrays) or the multiply against a cached operand (Plan::pre).
+enum { CYC_MUL = 0, CYC_SQR = 1, CYC_PRE = 2 };
+// the scratch sum of 2n canonical coefficients below 2^N, bits1 apart: below 2^((2n - 1) bits1 + N + 1)
+static u64 cyc_scratch_limbs(const Plan &P) { return ((u64)(2 * P.n - 1) * P.bits1 + P.N + 1 + 63) / 64; }
+static const int CYC_V = 8;   // k_cwrap: limbs per thread, 256 threads (the ticket atomics bound it: 4 -> 8 halves them)
+static long cyc_blocks(long L) { return (L + 256 * CYC_V - 1) / (256 * CYC_V); }
+static const int CYC_XW = 2;  // words behind k_cwrap's flags that start as 0: the ticket counter and the overflow O
+// k_cwrap's region: a look-back flag per block, the CYC_XW words, and a word per block ("a limb above limb 0
+// is not all-ones": written by every block, never cleared)
+static long cyc_flag_region_words(long L) { return 2 * cyc_blocks(L) + CYC_XW; }
+
+static int make_plan_cyc(Plan *p, long L, unsigned long depth, unsigned long w, int kind)
+{
+    memset(p, 0, sizeof(*p));
+    if (L < 1 || depth < 2 || depth > 30 || w < 1 || w > 4096) return MPFFT_EINVAL;
+    if (kind != CYC_MUL && kind != CYC_SQR && kind != CYC_PRE) return MPFFT_EINVAL;
+    const u64 n2 = (u64)2 << depth, N = ((u64)1 << depth) * w, B = 64 * (u64)L;
+    if (N % 64 || B % n2) return MPFFT_EINVAL;
+    if (N / 64 > 4096) return MPFFT_EUNSUPPORTED;
+    const u64 b = B / n2;
+    if (2 * b + depth + 1 > N) return MPFFT_ETOOBIG;
+    int rc = make_plan_split(p, 1, 1, depth, w, false, -1);
+    if (rc) return rc;
+    if (p->rpass && (p->l == 2048 || p->l == 4096)) {   // make_plan's split where nothing is truncated
+        Plan q;
+        if (make_plan_split(&q, 1, 1, depth, w, false, (int)depth / 2 + 1, p->l == 2048) == MPFFT_OK && q.rpass) *p = q;
+    }
+    p->cyc = true;
+    p->n1 = p->n2 = L;
+    p->bits1 = b;
+    p->j1 = p->j2 = p->len = p->trunc = 2 * p->n;
+    p->Tr = p->NR;
+    p->fold = 0;
+    p->ltw = false;
+    p->fuse_scale = p->wave;   // as make_plan_split's at Tr = NR
+    p->total = (long)cyc_scratch_limbs(*p);
+    if (kind != CYC_MUL) plan_drop_b(p, kind == CYC_SQR);
+    size_t o = p->off_flags;
+    o += align_up((size_t)(p->total / 256 + 8) * 4, 256);
+    p->off_nflags = o; o += align_up((size_t)cyc_flag_region_words(L) * 4, 256);
     p->off_meta = o; o += align_up((size_t)p->slots * 4, 256);
     p->off_nscr = o; o += align_up((size_t)p->total * 8, 256);
     p->bytes = o;
