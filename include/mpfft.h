@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 6
+#define MPFFT_VERSION 7
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -119,7 +119,7 @@ int mpfft_sqr_stage_kernels(long n, unsigned long depth, unsigned long w, char *
  * Limits: a negacyclic transform cannot be truncated, so with power-of-two w the fully
  * efficient moduli lie a factor 2 apart (B ~ n^2 w); for B a power of two (Fermat numbers) the
  * pieces are N/4 bits, not N/2, and the slot count equals that of the multiply-and-fold route
- * (the reference's low-limb CRT trick, which would close that gap, is not implemented).
+ * (the reference's low-limb CRT trick closes that gap: the mpfft_mulmodw_* entries below).
  * Not covered: the sqrt2 front end, the sharded / multi-GPU entries and
  * mpfft_set_devices routing -- these always run on the calling thread's device. */
 int mpfft_mulmod_check_params(long L, unsigned long depth, unsigned long w);
@@ -272,6 +272,50 @@ int mpfft_mulmodm1_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t 
                                   unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
 int mpfft_mulmodm1_mul_precomp_device(uint64_t *d_r, const uint64_t *d_a, const void *d_pre, size_t pre_bytes, long L,
                                       unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---- products mod 2^B + 1 with the low-word CRT (MPFFT_VERSION 7): mpfft_mulmod_*'s product with
+ * pieces of up to N / 2 + 15 bits, so a power-of-two B (Fermat numbers, Pepin tests, nested
+ * Schoenhage-Strassen) runs at bits1 = N / 2: half the transform of mpfft_mulmod_* at the same B.
+ * Beside the transform, which gives the coefficients mod p = 2^N + 1, the negacyclic convolution of
+ * the pieces' low 32-bit words is computed mod 2^32 (k_nlowconv: 4 n^2 32-bit multiply-adds; the
+ * reference's fft_naive_convolution_1 with 32-bit words in place of limbs).  p == 1 (mod 2^32), so
+ * the difference of the two, a signed 32-bit word, is floor(c_k / p), and c_k is exact while
+ * |c_k| < 2^(N + 31).
+ * Operands, result and the rules for r, d_r and the workspace are mpfft_mulmod_*'s.  Valid
+ * (L, depth, w): as mpfft_mulmod_check_params with two changes: the bound is
+ * 2 bits1 + depth + 2 <= N + 32 (MPFFT_ETOOBIG), and bits1 >= 32 is required (MPFFT_EINVAL): below
+ * that the 32-bit words of neighbouring pieces would overlap in the fold, and mpfft_mulmod_* already
+ * serves those shapes (2 bits1 + depth + 2 <= 68 <= N + 4 there).  Results are limb-equal to
+ * mpfft_mulmod_*'s wherever both are valid.
+ * Not covered: the same trick mod 2^B - 1, the cached operand for this family, the sqrt2 front
+ * end, the sharded / multi-GPU entries and mpfft_set_devices routing, and fusing the weight or the
+ * un-weight into the column passes. */
+int mpfft_mulmodw_check_params(long L, unsigned long depth, unsigned long w);
+int mpfft_mulmodw_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w);
+int mpfft_sqrmodw_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w);
+int mpfft_mulmodw_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                         unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+int mpfft_sqrmodw_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                         void *d_ws, size_t ws_bytes, void *stream);
+size_t mpfft_mulmodw_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr);   /* 0 on invalid parameters */
+int mpfft_mulmodw_plan_info(long L, unsigned long depth, unsigned long w, long *out);
+/* out[9]: the eight entries of mpfft_mulmod_workspace_layout, then the byte offset of the low-word
+ * convolution d (2n uint32). */
+int mpfft_mulmodw_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out);
+/* One stage on the workspace (tests), as mpfft_mulmod_stage, with MPFFT_STAGE_LOWCONV: d from the
+ * operands d_a, d_b (sqr: d_a alone); MPFFT_STAGE_COMBINE reads the canonical slots and d from the
+ * workspace.  (MPFFT_STAGE_LOWCONV on mpfft_mulmod_stage returns MPFFT_EINVAL.) */
+#define MPFFT_STAGE_LOWCONV 9
+int mpfft_mulmodw_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                        unsigned long depth, unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream);
+/* As mpfft_mulmod_stage_kernels; the combine field names k_nlowconv and k_nwrapw.  Under
+ * mpfft_profile_begin/end the low-word convolution counts with the combine stage. */
+int mpfft_mulmodw_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len);
+/* As mpfft_mulmod_choose / mpfft_mulmod_next_size under this family's bound, the predicted time
+ * plus the convolution's 4 n^2 multiply-adds at a measured cost each.  No (depth, w) is valid
+ * for L < 4 (bits1 >= 32 at 2n = 8): mpfft_mulmodw_choose returns MPFFT_EINVAL there. */
+int mpfft_mulmodw_choose(long L, unsigned long *depth, unsigned long *w);
+int mpfft_mulmodw_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity

@@ -266,6 +266,33 @@ def lib():
             h.mpfft_mulmodm1_precomp_device.restype = ctypes.c_int
             h.mpfft_mulmodm1_mul_precomp_device.argtypes = [_vp, _vp, _vp, _sz, _L, _UL, _UL, _vp, _sz, _vp]
             h.mpfft_mulmodm1_mul_precomp_device.restype = ctypes.c_int
+        if hasattr(h, "mpfft_mulmodw_ex"):   # MPFFT_VERSION 7 (older libraries in A/B runs lack them)
+            _ulp = ctypes.POINTER(ctypes.c_ulong)
+            h.mpfft_mulmodw_check_params.argtypes = [_L, _UL, _UL]
+            h.mpfft_mulmodw_check_params.restype = ctypes.c_int
+            h.mpfft_mulmodw_ex.argtypes = [_u64p, _u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_mulmodw_ex.restype = ctypes.c_int
+            h.mpfft_sqrmodw_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
+            h.mpfft_sqrmodw_ex.restype = ctypes.c_int
+            h.mpfft_mulmodw_device.argtypes = [_vp, _vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
+            h.mpfft_mulmodw_device.restype = ctypes.c_int
+            h.mpfft_sqrmodw_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
+            h.mpfft_sqrmodw_device.restype = ctypes.c_int
+            h.mpfft_mulmodw_workspace_bytes.argtypes = [_L, _UL, _UL, ctypes.c_int]
+            h.mpfft_mulmodw_workspace_bytes.restype = ctypes.c_size_t
+            h.mpfft_mulmodw_plan_info.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
+            h.mpfft_mulmodw_plan_info.restype = ctypes.c_int
+            h.mpfft_mulmodw_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
+            h.mpfft_mulmodw_workspace_layout.restype = ctypes.c_int
+            h.mpfft_mulmodw_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _UL, _UL, ctypes.c_int, _vp,
+                                              ctypes.c_size_t, _vp]
+            h.mpfft_mulmodw_stage.restype = ctypes.c_int
+            h.mpfft_mulmodw_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
+            h.mpfft_mulmodw_stage_kernels.restype = ctypes.c_int
+            h.mpfft_mulmodw_choose.argtypes = [_L, _ulp, _ulp]
+            h.mpfft_mulmodw_choose.restype = ctypes.c_int
+            h.mpfft_mulmodw_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
+            h.mpfft_mulmodw_next_size.restype = ctypes.c_int
         _lib = h
     return _lib
 
@@ -829,6 +856,138 @@ def mulmod_next_size(min_L):
     rc = lib().mpfft_mulmod_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
     if rc:
         raise MpfftError(rc, f"mulmod_next_size({min_L})")
+    return int(L.value), int(d.value), int(w.value)
+
+
+# ---- products mod 2^B + 1 with the low-word CRT (mpfft_mulmodw_*, include/mpfft.h): the mulmod
+# functions' mirrors, valid up to 2 bits1 + depth + 2 <= N + 32 (and from bits1 = 32 on) ----
+STAGE_LOWCONV = 9   # mulmodw_stage: the low-word convolution d from the operands
+
+
+def mulmodw_check_params(L, depth, w):
+    return lib().mpfft_mulmodw_check_params(L, depth, w)
+
+
+def mulmodw(a, b, depth, w):
+    """a b mod 2^(64 L) + 1 for L + 1-limb fully reduced a, b: a new uint64 array of L + 1 limbs."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    if len(a) != len(b) or len(a) < 2:
+        raise ValueError("operands are L + 1 limbs each")
+    L = len(a) - 1
+    r = np.zeros(L + 1, dtype=np.uint64)
+    rc = lib().mpfft_mulmodw_ex(_p(r), _p(a), _p(b), L, depth, w)
+    if rc:
+        raise MpfftError(rc, f"mulmodw(L={L}, depth={depth}, w={w})")
+    return r
+
+
+def sqrmodw(a, depth, w):
+    """a^2 mod 2^(64 L) + 1 (one forward transform)."""
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if len(a) < 2:
+        raise ValueError("the operand is L + 1 limbs")
+    L = len(a) - 1
+    r = np.zeros(L + 1, dtype=np.uint64)
+    rc = lib().mpfft_sqrmodw_ex(_p(r), _p(a), L, depth, w)
+    if rc:
+        raise MpfftError(rc, f"sqrmodw(L={L}, depth={depth}, w={w})")
+    return r
+
+
+def mulmodw_workspace_bytes(L, depth, w, sqr=False):
+    return int(lib().mpfft_mulmodw_workspace_bytes(L, depth, w, int(bool(sqr))))
+
+
+def alloc_workspace_mulmodw(L, depth, w, sqr=False, device="cuda"):
+    import torch
+    nb = mulmodw_workspace_bytes(L, depth, w, sqr)
+    if nb == 0:
+        raise MpfftError(mulmodw_check_params(L, depth, w), "mulmodw workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def mulmodw_device(d_r, d_a, d_b, L, depth, w, ws, stream=None):
+    """d_r[:L+1] = d_a d_b mod 2^(64 L) + 1 on the GPU; queued on `stream`, not synchronised.
+    d_r may not be an operand (it may be the next call's)."""
+    rc = lib().mpfft_mulmodw_device(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws),
+                                    ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmodw_device")
+
+
+def sqrmodw_device(d_r, d_a, L, depth, w, ws, stream=None):
+    rc = lib().mpfft_sqrmodw_device(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws),
+                                    ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_sqrmodw_device")
+
+
+def mulmodw_plan_info(L, depth, w):
+    out = (ctypes.c_long * 10)()
+    rc = lib().mpfft_mulmodw_plan_info(L, depth, w, out)
+    if rc:
+        raise MpfftError(rc, f"mulmodw plan(L={L}, depth={depth}, w={w})")
+    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
+    return dict(zip(keys, list(out)))
+
+
+def mulmodw_workspace_layout(L, depth, w, sqr=False):
+    out = (ctypes.c_size_t * 9)()
+    rc = lib().mpfft_mulmodw_workspace_layout(L, depth, w, int(bool(sqr)), out)
+    if rc:
+        raise MpfftError(rc, "mulmodw_workspace_layout")
+    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw", "d")
+    return dict(zip(keys, list(out)))
+
+
+def mulmodw_workspace_views(ws, L, depth, w, sqr=False):
+    """(digA, topA, cbA, d) views into a mulmodw workspace tensor (slot-major): limbs (slots, l) int64,
+    carry limbs int32, carry masks (slots, cbw) int64, and the low-word convolution d, (slots,) int32
+    (the words mod 2^32)."""
+    import torch
+    P = mulmodw_plan_info(L, depth, w)
+    lay = mulmodw_workspace_layout(L, depth, w, sqr)
+    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
+    u8 = ws.view(torch.uint8)
+    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
+    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
+    cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
+    d = u8[lay["d"]:lay["d"] + slots * 4].view(torch.int32)
+    return dig, top, cb, d
+
+
+def mulmodw_stage(which, d_a, d_b, d_r, L, depth, w, ws, sqr=False, stream=None):
+    rc = lib().mpfft_mulmodw_stage(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, int(bool(sqr)), _ptr(ws),
+                                   ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_mulmodw_stage({which})")
+
+
+def mulmodw_stage_kernels(L, depth, w, sqr=False):
+    """dict stage -> the kernel a product mod 2^(64 L) + 1 launches for it"""
+    buf = ctypes.create_string_buffer(512)
+    rc = lib().mpfft_mulmodw_stage_kernels(L, depth, w, int(bool(sqr)), buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_mulmodw_stage_kernels")
+    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+
+
+def mulmodw_choose(L):
+    """(depth, w) of least predicted time that are valid for this L."""
+    d, w = ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_mulmodw_choose(L, ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"mulmodw_choose(L={L})")
+    return int(d.value), int(w.value)
+
+
+def mulmodw_next_size(min_L):
+    """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
+    L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_mulmodw_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"mulmodw_next_size({min_L})")
     return int(L.value), int(d.value), int(w.value)
 
 

@@ -1179,6 +1179,62 @@ struct Exec {
         return launch(k_nfix, dim3(1), dim3(1024), 0, r, (long)P.n1, (const u32 *)st, a.nblk);
     }
 
+    // ---- the low-word CRT family (negaw.hpp) on a make_plan_mod plan with Plan::lowcrt --------
+    // d <- the negacyclic convolution mod 2^32 of the operands' piece low words (srcB == srcA: a square).
+    // Enough workgroups to fill the device: the terms are split over blockIdx.y where the outputs alone
+    // give fewer than LC_BLOCKS.
+    int nlowconv(const u64 *srcA, const u64 *srcB, unsigned char *ws)
+    {
+        constexpr long LC_BLOCKS = 2048;
+        LowConvArgs a;
+        memset(&a, 0, sizeof(a));
+        a.src[0] = srcA;
+        a.src[1] = srcB;
+        a.L = P.n1;
+        a.bits1 = P.bits1;
+        a.len = P.len;
+        a.d = (u32 *)(ws + P.off_lowd);
+        const long kt = (P.len + LC_TK - 1) / LC_TK, nch = (P.len + LC_TI - 1) / LC_TI;
+        const long split = std::min(nch, std::max(1L, LC_BLOCKS / kt));
+        a.ichunks = (int)((nch + split - 1) / split);
+        const long gy = (nch + a.ichunks - 1) / a.ichunks;
+        HIPCHK(hipMemsetAsync(a.d, 0, (size_t)P.len * 4, s));
+        return launch(k_nlowconv, dim3((unsigned)kt, (unsigned)gy), dim3(LC_NT), 0, a);
+    }
+
+    // the fold with the low-word CRT: k_combine1 into the scratch, k_nwrapw (reads the canonical slots
+    // and d), k_nfix; r: L + 1 limbs
+    int ncombinew(u64 *r, unsigned char *ws)
+    {
+        u64 *T = (u64 *)(ws + P.off_nscr);
+        u32 *st = (u32 *)(ws + P.off_nflags);
+        const bool cleared = zflags == comb_flags(ws);
+        int rc = combine_single(T, ws);
+        if (rc) return rc;
+        NegaWCombArgs aw;
+        memset(&aw, 0, sizeof(aw));
+        NegaCombArgs &a = aw.b;
+        a.T = T;
+        a.TL = P.total;
+        a.dig = row.dig[0];
+        a.top = row.top[0];
+        a.l = (int)P.l;
+        a.N = P.N;
+        a.bits1 = P.bits1;
+        a.L = P.n1;
+        a.len = P.len;
+        a.nT = (int)((P.total + P.n1 - 1) / P.n1);
+        a.qmax = (int)(((u64)(P.len - 1) * P.bits1 + P.N + 31) / (64 * (u64)P.n1));
+        // negative pieces: the odd T_i, C, the odd Wb_q and Eb_q, the even Cb_q
+        a.K = 2u * (u32)(a.nT / 2 + 1 + 2 * ((a.qmax + 1) / 2) + a.qmax / 2 + 1);
+        a.inv_bits1 = 1.0 / (double)P.bits1;
+        a.nblk = nega_blocks(P.n1);
+        aw.d = (const u32 *)(ws + P.off_lowd);
+        if (!cleared) HIPCHK(hipMemsetAsync(st, 0, (size_t)(a.nblk + 2) * 4, s));
+        if ((rc = launch(k_nwrapw<NEGA_V>, dim3((unsigned)a.nblk), dim3(256), 0, aw, r, st))) return rc;
+        return launch(k_nfix, dim3(1), dim3(1024), 0, r, (long)P.n1, (const u32 *)st, a.nblk);
+    }
+
     // ---- the cyclic top level (cyc.hpp) on a make_plan_cyc plan ---------------------------
     // words of both combine flag regions from comb_flags() on (the first forward column pass clears them)
     static long cyc_flag_words(const Plan &P) { return (long)((P.off_nflags - P.off_flags) / 4) + cyc_blocks(P.n1) + CYC_XW; }

@@ -34,6 +34,7 @@
 #include "combine.hpp"
 #include "fold.hpp"
 #include "nega.hpp"
+#include "negaw.hpp"
 #include "cyc.hpp"
 #include "wdispatch.hpp"
 #include "bdispatch.hpp"
@@ -290,7 +291,9 @@ static int run_all_mod(const Plan &P, u64 *d_r, const u64 *d_a, const u64 *d_b, 
     pc.mark(5, s);
     if ((rc = X.unweight())) return rc;
     pc.mark(6, s);
-    rc = X.ncombine(d_r, ws);
+    // the low-word CRT family (negaw.hpp): the low-word convolution counts with the combine stage
+    if (P.lowcrt && (rc = X.nlowconv(d_a, d_b, ws))) return rc;
+    rc = P.lowcrt ? X.ncombinew(d_r, ws) : X.ncombine(d_r, ws);
     pc.mark(7, s);
     return rc;
 }
@@ -377,7 +380,8 @@ static std::string stage_kernel_names(const Plan &P)
         if (X.unweight_rscale()) snprintf(unw, sizeof unw, "k_rscale (un-weight: exponent per slot)");
         else snprintf(unw, sizeof unw, "k_nunweight<%d>", X.nega_u());
         return std::string(fwdc) + ';' + rows + ';' + pw + ';' + pass + ';' + invc + ';' + unw + ';'
-               + "k_combine1 + k_nwrap + k_nfix (negacyclic)";
+               + (P.lowcrt ? "k_nlowconv + k_combine1 + k_nwrapw + k_nfix (negacyclic, low-word CRT)"
+                           : "k_combine1 + k_nwrap + k_nfix (negacyclic)");
     }
     return std::string(fwdc) + ';' + rows + ';' + pw + ';' + pass + ';' + invc + ';' + scale + ';' + comb;
 }
@@ -1127,43 +1131,45 @@ void mpfft_precomp_destroy(mpfft_pre *pre)
 }
 
 // ---- products mod 2^B + 1 (nega.hpp, make_plan_mod, run_all_mod).  Out of scope as for the
-// squares: the sqrt2 front end, the sharded and multi-GPU entries, mpfft_set_devices routing. --
-int mpfft_mulmod_check_params(long L, unsigned long depth, unsigned long w)
-{
-    Plan P;
-    return make_plan_mod(&P, L, depth, w, false);
-}
+// squares: the sqrt2 front end, the sharded and multi-GPU entries, mpfft_set_devices routing.
+// Two entry families over the same code, told apart by make_plan_mod's crt: mpfft_mulmod_* (the
+// signs read back from the residues) and mpfft_mulmodw_* (the low-word CRT, negaw.hpp; the cached
+// operand is out of scope there too). -------------------------------------------------------------
+} // extern "C"
 
-size_t mpfft_mulmod_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr)
+static size_t mod_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr, bool crt)
 {
     Plan P;
-    if (make_plan_mod(&P, L, depth, w, sqr != 0)) return 0;
+    if (make_plan_mod(&P, L, depth, w, sqr != 0, crt)) return 0;
     return P.bytes;
 }
 
-int mpfft_mulmod_plan_info(long L, unsigned long depth, unsigned long w, long *out)
+static int mod_plan_info(long L, unsigned long depth, unsigned long w, long *out, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, false);
+    int rc = make_plan_mod(&P, L, depth, w, false, crt);
     if (rc) return rc;
     plan_info_out(P, out);
     return MPFFT_OK;
 }
 
-int mpfft_mulmod_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out)
+// out[8], and on the low-word CRT family out[8]: the byte offset of d
+static int mod_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, sqr != 0);
+    int rc = make_plan_mod(&P, L, depth, w, sqr != 0, crt);
     if (rc) return rc;
     layout_out(P, out);
+    if (crt) out[8] = P.off_lowd;
     return MPFFT_OK;
 }
 
-int mpfft_mulmod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
-                        unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+// d_b == d_a on a squaring plan
+static int mod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                      unsigned long w, bool sqr, void *d_ws, size_t ws_bytes, void *stream, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, false);
+    int rc = make_plan_mod(&P, L, depth, w, sqr, crt);
     if (rc) return rc;
     if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
     if (d_r == d_a || d_r == d_b) return MPFFT_EINVAL;
@@ -1171,41 +1177,33 @@ int mpfft_mulmod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b,
     return run_all_mod(P, d_r, d_a, d_b, (unsigned char *)d_ws, (hipStream_t)stream);
 }
 
-int mpfft_sqrmod_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
-                        void *d_ws, size_t ws_bytes, void *stream)
+static int mod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L, unsigned long depth,
+                     unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, true);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (d_r == d_a) return MPFFT_EINVAL;
-    (void)hipGetLastError();
-    return run_all_mod(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream);
-}
-
-int mpfft_mulmod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
-                       unsigned long depth, unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream)
-{
-    Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, sqr != 0);
+    int rc = make_plan_mod(&P, L, depth, w, sqr != 0, crt);
     if (rc) return rc;
     if ((stage & MPFFT_STAGE_DRIVEN) || stage == MPFFT_STAGE_FOLD_COMBINE) return MPFFT_EINVAL;
-    if (stage != MPFFT_STAGE_FWD_COLUMNS && stage != MPFFT_STAGE_SCALE && stage != MPFFT_STAGE_COMBINE)
+    if (stage == MPFFT_STAGE_LOWCONV && !crt) return MPFFT_EINVAL;
+    if (stage != MPFFT_STAGE_FWD_COLUMNS && stage != MPFFT_STAGE_SCALE && stage != MPFFT_STAGE_COMBINE
+        && stage != MPFFT_STAGE_LOWCONV)
         return single_stage(P, stage, d_a, sqr ? d_a : d_b, d_r, d_ws, ws_bytes, stream);   // the multiply's, Tr = NR
     if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
     (void)hipGetLastError();
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
     if (stage == MPFFT_STAGE_SCALE) return X.unweight();
-    if (stage == MPFFT_STAGE_COMBINE) return X.ncombine(d_r, (unsigned char *)d_ws);
+    if (stage == MPFFT_STAGE_LOWCONV) return X.nlowconv(d_a, sqr ? d_a : d_b, (unsigned char *)d_ws);
+    if (stage == MPFFT_STAGE_COMBINE)
+        return crt ? X.ncombinew(d_r, (unsigned char *)d_ws) : X.ncombine(d_r, (unsigned char *)d_ws);
     if ((rc = X.nweight(d_a, sqr ? d_a : d_b, fwd_nops(P)))) return rc;
     return X.fwd_columns(nullptr, 0, nullptr, 0, fwd_nops(P), fwd_op(P));
 }
 
-int mpfft_mulmod_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len)
+static int mod_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, sqr != 0);
+    int rc = make_plan_mod(&P, L, depth, w, sqr != 0, crt);
     if (rc) return rc;
     return copy_out(stage_kernel_names(P), buf, len);
 }
@@ -1246,26 +1244,20 @@ static int mulmod_host(const Plan &P, uint64_t *r, const uint64_t *a, const uint
     return MPFFT_OK;
 }
 
-int mpfft_mulmod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w)
+static int mod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w,
+                  bool sqr, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, false);
+    int rc = make_plan_mod(&P, L, depth, w, sqr, crt);
     if (rc) return rc;
     return mulmod_host(P, r, a, b);
 }
 
-int mpfft_sqrmod_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w)
-{
-    Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, true);
-    if (rc) return rc;
-    return mulmod_host(P, r, a, a);
-}
-
-// mpfft_choose's candidates; a candidate's cost is choose_cost at its 2n slots, whatever L.
+// mpfft_choose's candidates; a candidate's cost is choose_cost at its 2n slots, whatever L (on the
+// low-word CRT family plus the convolution's 4 n^2 multiply-adds).
 // fixed_L > 0: the candidates valid for that L; else each candidate at its smallest valid
-// L >= min_L (a multiple of its granularity 2n / 64)
-static int mulmod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w)
+// L >= min_L (a multiple of its granularity 2n / 64; crt: at least n limbs, bits1 >= 32)
+static int mulmod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w, bool crt = false)
 {
     double best = -1.0;
     for (unsigned long d = 2; d <= 24; ++d)
@@ -1274,9 +1266,10 @@ static int mulmod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, 
             if (N % 64) continue;
             if (N / 64 > 4096) break;
             const long g = std::max<long>(1, (2L << d) / 64);
-            const long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
+            long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
+            if (crt && fixed_L <= 0) Lc = std::max(Lc, 1L << d);
             Plan P;
-            if (make_plan_mod(&P, Lc, d, wv, false)) continue;
+            if (make_plan_mod(&P, Lc, d, wv, false, crt)) continue;
             const double c = choose_cost(P);
             if (best < 0 || c < best) {
                 best = c;
@@ -1285,7 +1278,64 @@ static int mulmod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, 
                 *w = wv;
             }
         }
-    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+    if (best < 0) return crt && fixed_L > 0 && fixed_L < 4 ? MPFFT_EINVAL : MPFFT_ETOOBIG;   // L < 4: no bits1 >= 32
+    return MPFFT_OK;
+}
+
+extern "C" {
+
+int mpfft_mulmod_check_params(long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_mod(&P, L, depth, w, false);
+}
+
+size_t mpfft_mulmod_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr)
+{
+    return mod_workspace_bytes(L, depth, w, sqr, false);
+}
+
+int mpfft_mulmod_plan_info(long L, unsigned long depth, unsigned long w, long *out)
+{
+    return mod_plan_info(L, depth, w, out, false);
+}
+
+int mpfft_mulmod_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out)
+{
+    return mod_workspace_layout(L, depth, w, sqr, out, false);
+}
+
+int mpfft_mulmod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                        unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    return mod_device(d_r, d_a, d_b, L, depth, w, false, d_ws, ws_bytes, stream, false);
+}
+
+int mpfft_sqrmod_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                        void *d_ws, size_t ws_bytes, void *stream)
+{
+    return mod_device(d_r, d_a, d_a, L, depth, w, true, d_ws, ws_bytes, stream, false);
+}
+
+int mpfft_mulmod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                       unsigned long depth, unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream)
+{
+    return mod_stage(stage, d_a, d_b, d_r, L, depth, w, sqr, d_ws, ws_bytes, stream, false);
+}
+
+int mpfft_mulmod_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len)
+{
+    return mod_stage_kernels(L, depth, w, sqr, buf, len, false);
+}
+
+int mpfft_mulmod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w)
+{
+    return mod_ex(r, a, b, L, depth, w, false, false);
+}
+
+int mpfft_sqrmod_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w)
+{
+    return mod_ex(r, a, a, L, depth, w, true, false);
 }
 
 int mpfft_mulmod_choose(long L, unsigned long *depth, unsigned long *w)
@@ -1299,6 +1349,74 @@ int mpfft_mulmod_next_size(long min_L, long *L, unsigned long *depth, unsigned l
 {
     if (min_L < 1) return MPFFT_EINVAL;
     return mulmod_pick(0, min_L, L, depth, w);
+}
+
+// the low-word CRT family (MPFFT_VERSION 7)
+int mpfft_mulmodw_check_params(long L, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_mod(&P, L, depth, w, false, true);
+}
+
+size_t mpfft_mulmodw_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr)
+{
+    return mod_workspace_bytes(L, depth, w, sqr, true);
+}
+
+int mpfft_mulmodw_plan_info(long L, unsigned long depth, unsigned long w, long *out)
+{
+    return mod_plan_info(L, depth, w, out, true);
+}
+
+int mpfft_mulmodw_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out)
+{
+    return mod_workspace_layout(L, depth, w, sqr, out, true);
+}
+
+int mpfft_mulmodw_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
+                         unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    return mod_device(d_r, d_a, d_b, L, depth, w, false, d_ws, ws_bytes, stream, true);
+}
+
+int mpfft_sqrmodw_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
+                         void *d_ws, size_t ws_bytes, void *stream)
+{
+    return mod_device(d_r, d_a, d_a, L, depth, w, true, d_ws, ws_bytes, stream, true);
+}
+
+int mpfft_mulmodw_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
+                        unsigned long depth, unsigned long w, int sqr, void *d_ws, size_t ws_bytes, void *stream)
+{
+    return mod_stage(stage, d_a, d_b, d_r, L, depth, w, sqr, d_ws, ws_bytes, stream, true);
+}
+
+int mpfft_mulmodw_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len)
+{
+    return mod_stage_kernels(L, depth, w, sqr, buf, len, true);
+}
+
+int mpfft_mulmodw_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w)
+{
+    return mod_ex(r, a, b, L, depth, w, false, true);
+}
+
+int mpfft_sqrmodw_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w)
+{
+    return mod_ex(r, a, a, L, depth, w, true, true);
+}
+
+int mpfft_mulmodw_choose(long L, unsigned long *depth, unsigned long *w)
+{
+    long Lc = 0;
+    if (L < 1) return MPFFT_EINVAL;
+    return mulmod_pick(L, 0, &Lc, depth, w, true);
+}
+
+int mpfft_mulmodw_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w)
+{
+    if (min_L < 1) return MPFFT_EINVAL;
+    return mulmod_pick(0, min_L, L, depth, w, true);
 }
 
 // ---- products mod 2^B - 1 (cyc.hpp, make_plan_cyc): run_all on a cyclic plan.  Out of scope as for

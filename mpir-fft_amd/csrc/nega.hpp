@@ -8,7 +8,7 @@
 //                    with even w take k_rscale's per-slot exponent instead)
 //   k_nwrap<V>       the scratch sum T = sum c~_j 2^(j bits1) of the canonical coefficients
 //                    (k_combine1) folded mod M with the signs read back: a decoupled look-back
-//                    carry chain over the L result limbs
+//                    carry chain over the L result limbs (nega_chain, shared with negaw.hpp)
 //   k_nfix           the end-around correction: minus the chain's overflow (2^B == -1)
 #pragma once
 #include "kernels.hpp"
@@ -168,15 +168,17 @@ __device__ __forceinline__ void nega_limb(const NegaCombArgs &a, long m, u64 *lo
     *hi = shi;
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void k_nwrap(NegaCombArgs a, u64 *r, u32 *st)
+// The chain over the L result limbs, shared by k_nwrap and k_nwrapw (negaw.hpp): limb(m, &lo, &hi)
+// gives the pieces' sum at result limb m; nblk blocks of 256 threads, V limbs per thread.
+template <int V, class LimbFn>
+__device__ __forceinline__ void nega_chain(long L, long nblk, LimbFn limb, u64 *r, u32 *st)
 {
     constexpr int NT = 256, BL = NT * V;
     __shared__ u32 H[NT + 1];
     __shared__ u64 scr[64];
     __shared__ u32 sh_cin, sh_b, sh_htop;
     const WG c = wg_ctx();
-    if (c.t == 0) sh_b = __hip_atomic_fetch_add(&st[a.nblk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c.t == 0) sh_b = __hip_atomic_fetch_add(&st[nblk], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
     const long b = sh_b;   // ticket: every block below it has started
     const long base = b * BL, mA = base + (long)c.t * V;
@@ -186,14 +188,14 @@ __global__ __launch_bounds__(256) void k_nwrap(NegaCombArgs a, u64 *r, u32 *st)
     for (int k = 0; k < V; ++k) {
         lo[k] = 0;
         hi[k] = 0;
-        if (mA + k < a.L) nega_limb(a, mA + k, &lo[k], &hi[k]);
-        if (mA + k == a.L - 1) sh_htop = hi[k];
+        if (mA + k < L) limb(mA + k, &lo[k], &hi[k]);
+        if (mA + k == L - 1) sh_htop = hi[k];
     }
     H[c.t + 1] = hi[V - 1];
     if (c.t == 0) {
         u64 l0 = 0;
         u32 h0 = 0;
-        if (base > 0) nega_limb(a, base - 1, &l0, &h0);
+        if (base > 0) limb(base - 1, &l0, &h0);
         H[0] = h0;
     }
     __syncthreads();
@@ -201,7 +203,7 @@ __global__ __launch_bounds__(256) void k_nwrap(NegaCombArgs a, u64 *r, u32 *st)
     bool G = false, Pa = true;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-        const bool real = mA + k < a.L;
+        const bool real = mA + k < L;
         const bool gk = add_ovf(lo[k], (u64)(k ? hi[k - 1] : H[c.t]), &v[k]) && real;
         const bool pk = v[k] == MPF_MAXL || !real;
         g |= (u32)gk << k;
@@ -235,10 +237,16 @@ __global__ __launch_bounds__(256) void k_nwrap(NegaCombArgs a, u64 *r, u32 *st)
     bool run = ci & 1;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-        if (mA + k < a.L) r[mA + k] = v[k] + (run ? 1 : 0);
+        if (mA + k < L) r[mA + k] = v[k] + (run ? 1 : 0);
         run = ((g >> k) & 1) || (((p >> k) & 1) && run);
     }
-    if (c.t == 0 && b == a.nblk - 1) st[a.nblk + 1] = sh_htop + co;   // what leaves limb L - 1
+    if (c.t == 0 && b == nblk - 1) st[nblk + 1] = sh_htop + co;   // what leaves limb L - 1
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_nwrap(NegaCombArgs a, u64 *r, u32 *st)
+{
+    nega_chain<V>(a.L, a.nblk, [&](long m, u64 *lo, u32 *hi) { nega_limb(a, m, lo, hi); }, r, st);
 }
 
 // r (L limbs, V < 2^B) <- V - O mod M, fully reduced, and the top limb r[L].  One workgroup: the

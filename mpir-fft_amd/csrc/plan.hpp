@@ -74,6 +74,10 @@ struct Plan {
     size_t off_nflags;  // k_nwrap's look-back flags, ticket counter and overflow word (behind off_flags:
                         // the weight launch clears both in one range)
     size_t off_nscr;    // the unsigned sum of the canonical coefficients (k_combine1's output), `total` limbs
+    // make_plan_mod with crt (negaw.hpp): pieces up to the low-word CRT's bound; off_lowd: the low-word
+    // convolution d, 2n u32, behind every region of the plain negacyclic plan
+    bool lowcrt;
+    size_t off_lowd;
     // make_plan_cyc: a product mod 2^(64 n1) - 1 as a length-2n cyclic convolution (cyc.hpp); off_nflags
     // and off_nscr hold k_cwrap's flags and the scratch sum as they do k_nwrap's on a negacyclic plan
     bool cyc;
@@ -398,7 +402,11 @@ static u64 nega_scratch_limbs(const Plan &P) { return ((u64)(2 * P.n - 1) * P.bi
 static const int NEGA_V = 4;   // k_nwrap: limbs per thread, 256 threads
 static long nega_blocks(long L) { return (L + 256 * NEGA_V - 1) / (256 * NEGA_V); }
 
-static int make_plan_mod(Plan *p, long L, unsigned long depth, unsigned long w, bool sqr)
+// crt: the low-word CRT family (mpfft_mulmodw_*, negaw.hpp): a convolution of the pieces' low 32-bit
+// words mod 2^32 recovers floor(c_k / p) as a signed 32-bit word, so the coefficients need only
+// 2 bits1 + depth + 2 <= N + 32 -- bits1 = N / 2 for a power-of-two B; bits1 >= 32 keeps those
+// words apart (below that the plain family serves the shape).
+static int make_plan_mod(Plan *p, long L, unsigned long depth, unsigned long w, bool sqr, bool crt = false)
 {
     memset(p, 0, sizeof(*p));
     if (L < 1 || depth < 2 || depth > 30 || w < 1 || w > 4096) return MPFFT_EINVAL;
@@ -406,7 +414,8 @@ static int make_plan_mod(Plan *p, long L, unsigned long depth, unsigned long w, 
     if (N % 64 || B % n2) return MPFFT_EINVAL;
     if (N / 64 > 4096) return MPFFT_EUNSUPPORTED;
     const u64 b = B / n2;
-    if (2 * b + depth + 2 > N) return MPFFT_ETOOBIG;
+    if (crt && b < 32) return MPFFT_EINVAL;
+    if (2 * b + depth + 2 > N + (crt ? 32 : 0)) return MPFFT_ETOOBIG;
     int rc = make_plan_split(p, 1, 1, depth, w, false, -1);
     if (rc) return rc;
     if (p->rpass && (p->l == 2048 || p->l == 4096)) {   // make_plan's split where nothing is truncated
@@ -428,6 +437,10 @@ static int make_plan_mod(Plan *p, long L, unsigned long depth, unsigned long w, 
     p->off_nflags = o; o += align_up((size_t)(nega_blocks(L) + 2) * 4, 256);
     p->off_meta = o; o += align_up((size_t)p->slots * 4, 256);
     p->off_nscr = o; o += align_up((size_t)p->total * 8, 256);
+    if (crt) {
+        p->lowcrt = true;
+        p->off_lowd = o; o += align_up((size_t)p->len * 4, 256);
+    }
     p->bytes = o;
     return MPFFT_OK;
 }
@@ -502,8 +515,17 @@ static int make_plan_cyc(Plan *p, long L, unsigned long depth, unsigned long w, 
 static const double CHOOSE_SLOT_NS[13] = {69.7, 26.6, 12.3, 10.4, 7.3, 6.6, 11.0, 13.2, 28.4, 98.2, 167.9, 270.0, 810.7};
 static const double CHOOSE_FIXED_MS = 0.045;
 
+// The low-word CRT family's extra term (Plan::lowcrt): k_nlowconv's 4 n^2 32-bit multiply-adds at
+// CHOOSE_LOWCONV_MAC_NS each, without which the small-w candidates (many short coefficients) would
+// look cheaper than they are.  Measured on MI355X by scripts/time_mulmodw.py
+// (profiles/r16/mulmodw_ab.json): the stage alone takes 0.044 / 0.106 / 0.330 ms at 2n = 16384 /
+// 32768 / 65536; the marginal cost between the two larger sizes is 6.96e-5 ns per multiply-add
+// (the smaller sizes carry the launch and the clearing of d, which CHOOSE_FIXED_MS stands for).
+static const double CHOOSE_LOWCONV_MAC_NS = 7.0e-5;
+
 static double choose_cost(const Plan &P)
 {
     const int k = ilog2(P.l);
-    return CHOOSE_FIXED_MS + (double)P.trunc * CHOOSE_SLOT_NS[k < 12 ? k : 12] * 1e-6;
+    const double conv = P.lowcrt ? (double)P.len * (double)P.len * CHOOSE_LOWCONV_MAC_NS * 1e-6 : 0.0;
+    return CHOOSE_FIXED_MS + (double)P.trunc * CHOOSE_SLOT_NS[k < 12 ? k : 12] * 1e-6 + conv;
 }
