@@ -396,6 +396,12 @@ __global__ __launch_bounds__(256) void k_comb_summary(const u32 *st, const u32 *
 // thread composing a contiguous run of them, thread 0 chaining the runs -- and, when it is
 // 1, adds it to the stripe's limbs (r + j SL, `stripe_m` bounds): every all-ones limb wraps to
 // zero up to the first one that does not (almost always the first).
+// Which products reach the add path (tests/combine_model.py on the planner's partitions): random
+// operands never do -- a stripe's carry-out needs a window sum to overflow its limb, about 2^-64
+// per boundary; all-ones operands do, through wholly all-ones stripes of every rank and, where a
+// stripe is longer than 256 limbs (l = 4096 at two ranks), through the chunk loop;
+// tests/test_gpu_combine_placed.py places the rest (every chunk edge, generate / propagate / kill
+// in one composition, more than 256 stripes).
 // --------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_stripe_carry(CombArgs a, long nst, const int *sums, u64 *r)
 {
