@@ -85,9 +85,15 @@ __host__ __device__ constexpr int pw_wpe()
 {
     return pw_lds_bytes(M, 1 << LK, 64 * M) * (1024 >> LK) <= 160 * 1024 ? 4 : 2;
 }
-// partner-word prefetch distance of pw_combine for that budget
+// partner-word prefetch distance of pw_combine for that budget: 14 words in flight.  With 16 and
+// pw_canon's branch (below) k_pwss<18,8,*> parked 5-12 words of operand B in scratch across A's
+// transform; 14 has no scratch in any instance and measured no slower (C3 6.729 against 6.777 ms
+// with 16, 6.717 with 12; C4 68.43 against 68.56: profiles/r17/pw_chain_ab.txt)
+#ifndef PW_PDW
+#define PW_PDW 14   // A/B builds
+#endif
 template <int M, int LK>
-__host__ __device__ constexpr int pw_pd() { return pw_wpe<M, LK>() == 4 ? 16 : 2 * M; }
+__host__ __device__ constexpr int pw_pd() { return pw_wpe<M, LK>() == 4 ? PW_PDW : 2 * M; }
 
 // Exchange format: thread t publishes its value as 2M 32-bit words, word k at
 // Xw[k K + t] (conflict-free for any rotation), top in TT[t]; where pw_group(K) = G > 1, also the
@@ -238,60 +244,95 @@ __host__ __device__ __forceinline__ void pw_combine(u64 (&L)[M], int &T, int &S,
 }
 
 // canonical residue of L + T 2^N' (== L - T): limbs in [0, 2^N'), returns 1 for 2^N' (L = 0)
-template <int M>
+// The limbs are below 2^N' < p' as they stand, so a small T only moves the low word unless that
+// word under- or overflows (~2^-32 per lane, as in pw_norm's device form): then L - T is the
+// residue and the flag is 0.  Only a lane whose low word wraps takes the two folds below (a
+// branch the wave skips otherwise); with PW_NORM_SPILL_ALL every lane does.  One form for the
+// host and the device.
+// FAST = false: the two folds on every lane, no branch.  The K = 256 kernels sit at their 128
+// VGPRs through the forward transforms, and a branch here that rewrites all M limbs changes what
+// the register allocator evicts there: with the branch at operand B's pw_canon as well,
+// k_pwss<18,8,0> parked 2 words of B's pieces in scratch across A's transform and k_pwss<20,9,0>
+// 3; with it at A's in the cached tight form, k_pwsp<20,9,*> 2 (profiles/r17/pw_chain_isa.txt).
+// Those two sites keep the plain form.
+template <bool PRE>
+__host__ __device__ constexpr bool pw_canon_fast_a(int K) { return !(PRE && pw_tight(K)); }
+template <int M, bool FAST = true>
 __host__ __device__ __forceinline__ int pw_canon(u64 (&L)[M], int T)
 {
-    i128 acc = -(i128)T;
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        acc += (i128)L[j];
-        L[j] = (u64)acc;
-        acc >>= 64;
+    if (FAST) {
+        const u32 w0 = (u32)L[0], n0 = w0 - (u32)T;
+        const bool wrap = PW_NORM_SPILL_ALL || (T > 0 ? w0 < (u32)T : (T < 0 ? n0 < 0u - (u32)T : false));
+        L[0] = (L[0] & ~0xffffffffull) | (wrap ? w0 : n0);
+        if (__builtin_expect(!wrap, 1)) return 0;
     }
-    const int c1 = (int)(i64)acc;   // value == L - c1 now, |c1| <= 1
-    acc = -(i128)c1;
+    // L - T = L' + c1 2^N' == L' - c1 (|c1| <= 1), then L' - c1 = L'' + c2 2^N': two 32-bit chains
+    // over the words, each adding a small constant sign-extended; c2 != 0: the second fold wrapped,
+    // the value is 2^N' == -1
+    int cf = -T;
 #pragma unroll
-    for (int j = 0; j < M; ++j) {
-        acc += (i128)L[j];
-        L[j] = (u64)acc;
-        acc >>= 64;
-    }
-    if ((i64)acc != 0) {   // the second fold wrapped: the value is 2^N' == -1
+    for (int pass = 0; pass < 2; ++pass) {
+        const u32 sx = cf < 0 ? ~0u : 0u;
+        u32 c = 0;
 #pragma unroll
-        for (int j = 0; j < M; ++j) L[j] = 0;
-        return 1;
+        for (int j = 0; j < M; ++j) {
+            const u32 lo = __builtin_addc((u32)L[j], j == 0 ? (u32)cf : sx, c, &c);
+            const u32 hi = __builtin_addc((u32)(L[j] >> 32), sx, c, &c);
+            L[j] = ((u64)hi << 32) | lo;
+        }
+        cf = -((int)c - (cf < 0 ? 1 : 0));
     }
-    return 0;
+    const u64 keep = cf != 0 ? 0ull : ~0ull;
+#pragma unroll
+    for (int j = 0; j < M; ++j) L[j] &= keep;
+    return cf != 0;
 }
 
 // L + T 2^N'  <-  (2^(N'/2) - 1) (L + T 2^N')  mod p'  (M even; lo, hi = the low and high
 // M/2 limbs of L):  2^(N'/2) (lo + hi 2^(N'/2) + T 2^N') == lo 2^(N'/2) - hi - T 2^(N'/2), so
-// the product is (T - hi - lo) + (lo - hi - T) 2^(N'/2): two interleaved chains, then the low
-// chain's carry (in [-2, 1]) rippled into the high half.  The new top is small (|T'| <= |T| + 3).
+// the product is (T - hi - lo) + (lo - hi - T) 2^(N'/2).  Each half is two 32-bit borrow chains
+// (T sign-extended over the half's words): (T - hi) - lo and (lo - hi) - T, the four run word by
+// word side by side, so that every v_subb has the other three between it and the next of its own
+// chain (gfx950: two wait states from a VALU's carry out to the VALU that reads it).  The low
+// half's carry a0 (in [-3, 0]) goes into the high half: into its low word alone unless that word
+// underflows (~2^-32 per lane), else rippled through the half.  The new top is small
+// (|T'| <= |T| + 3).
 template <int M>
 __host__ __device__ __forceinline__ void pw_sqrt2(u64 (&L)[M], int &T)
 {
     static_assert(M % 2 == 0, "the half swap needs an even limb count");
     constexpr int H = M / 2;
-    i128 a0 = (i128)T, a1 = -(i128)T;
+    const u32 tx = T < 0 ? ~0u : 0u;
+    u32 b1 = 0, b2 = 0, b3 = 0, b4 = 0;
 #pragma unroll
     for (int j = 0; j < H; ++j) {
         const u64 lo = L[j], hi = L[j + H];
-        a0 += -(i128)hi - (i128)lo;
-        a1 += (i128)lo - (i128)hi;
-        L[j] = (u64)a0;
-        L[j + H] = (u64)a1;
-        a0 >>= 64;
-        a1 >>= 64;
-    }
-    i128 c = a0;
+        u32 r[2], s[2];
 #pragma unroll
-    for (int j = H; j < M; ++j) {
-        c += (i128)L[j];
-        L[j] = (u64)c;
-        c >>= 64;
+        for (int e = 0; e < 2; ++e) {
+            const u32 lw = (u32)(lo >> (32 * e)), hw = (u32)(hi >> (32 * e)), tw = j == 0 && e == 0 ? (u32)T : tx;
+            r[e] = __builtin_subc(__builtin_subc(tw, hw, b1, &b1), lw, b2, &b2);
+            s[e] = __builtin_subc(__builtin_subc(lw, hw, b3, &b3), tw, b4, &b4);
+        }
+        L[j] = ((u64)r[1] << 32) | r[0];
+        L[j + H] = ((u64)s[1] << 32) | s[0];
     }
-    T = (int)(i64)(a1 + c);
+    // T - hi - lo = low half + a0 2^(N'/2);  lo - hi - T = high half + a1 2^(N'/2)
+    const int a0 = (T < 0 ? -1 : 0) - (int)b1 - (int)b2, a1 = (T < 0 ? 1 : 0) - (int)b3 - (int)b4;
+    const u32 h0 = (u32)L[H], d0 = 0u - (u32)a0;   // a0 <= 0
+    const bool wrap = h0 < d0;
+    L[H] = (L[H] & ~0xffffffffull) | (wrap ? h0 : h0 - d0);
+    T = a1;
+    if (__builtin_expect(wrap, 0)) {   // rare: a0 < 0 borrows out of the high half's low word
+        u32 c = 0;
+#pragma unroll
+        for (int j = H; j < M; ++j) {
+            const u32 lw = __builtin_addc((u32)L[j], j == H ? (u32)a0 : ~0u, c, &c);
+            const u32 hw = __builtin_addc((u32)(L[j] >> 32), ~0u, c, &c);
+            L[j] = ((u64)hw << 32) | lw;
+        }
+        T = a1 + (int)c - 1;
+    }
 }
 
 // The product's limbs go to `Z`: registers (u64 (&)[M]) or, on the device, this thread's word
@@ -716,6 +757,9 @@ __device__ __forceinline__ void pw_level(u64 (&L)[M], int &T, int &S, unsigned &
     } else {
         // top / sign and pending exponent in one word (pw_pack_tp)
         T = pw_norm<M>(L, T);
+        // (the partner's word by a wave shuffle ahead of the publish in the in-wave levels, as the
+        // tight form takes it, measured no faster than this round trip: C3 6.7105 against 6.7169 ms
+        // at equal prefetch distance, profiles/r17/pw_chain_ab.txt)
         pw_publish_words<M, LK>(L, Xw, t);
         TT[t] = (int)((unsigned)(2 * T + S) << 12 | P);
         if (cross) __syncthreads(); else pw_wave_sync();
@@ -1095,7 +1139,7 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
     pw_stamp(stamp, t, 3);
 
     // ---- inner products: 2^Pa xa * 2^Pb xb = 2^(Pa + Pb) (xa xb) ---------------------
-    const int ca = pw_canon<M>(La, Ta);
+    const int ca = pw_canon<M, pw_canon_fast_a<PRE>(K)>(La, Ta);
     if constexpr (PRE) {
         // the record after A's pw_canon: its M limbs are not live across that (k_pwsp's register peak)
         static_assert(!PRE || late_b, "the cached form loads its record here");
@@ -1105,7 +1149,7 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
         // Pa, Pb the l = 4096 forms spilled a register)
         Tb = pw_launder((int)pw_pre_pack(0, Sa ^ Sb, pw_mod(Pa + Pb, N2)));
     } else {
-        cb = pw_canon<M>(Lb, Tb);
+        cb = pw_canon<M, false>(Lb, Tb);
     }
     u64 Z[M];
     int Tz, Sz = Sa ^ Sb;
@@ -1526,7 +1570,7 @@ __device__ __forceinline__ void pw_slot_precomp(u64 (&Lb)[M], int Tb, u32 *Xw, i
     pw_stamp(stamp, t, 1);
     pw_transform<M, LK, 0>(Lb, Tb, Sb, Pb, Xw, TT, W2, t);
     pw_stamp(stamp, t, 2);
-    const int cb = pw_canon<M>(Lb, Tb);
+    const int cb = pw_canon<M, false>(Lb, Tb);
     u64 *rec = (u64 *)(pre + (size_t)slot * pw_pre_slot_bytes(M, K));
 #pragma unroll
     for (int j = 0; j < M; ++j) rec[j * K + t] = Lb[j];
