@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 7
+#define MPFFT_VERSION 8
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -316,6 +316,64 @@ int mpfft_mulmodw_stage_kernels(long L, unsigned long depth, unsigned long w, in
  * for L < 4 (bits1 >= 32 at 2n = 8): mpfft_mulmodw_choose returns MPFFT_EINVAL there. */
 int mpfft_mulmodw_choose(long L, unsigned long *depth, unsigned long *w);
 int mpfft_mulmodw_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w);
+
+/* ---- sums of products (MPFFT_VERSION 8): r[0 .. n1 + n2 + 1) = sum_{i < K} a_i[0 .. n1) b_i[0 .. n2),
+ * 1 <= K <= MPFFT_DOT_MAX, exact, single device, with new_mpn_mul's meaning of (depth, w).  Between
+ * the forward and the inverse transforms a product is a slot-wise operation on residues mod
+ * 2^N + 1, and that stage is linear: every term runs its own forward transforms and pointwise
+ * product, the products are added slot-wise in a third coefficient array C, and the inverse
+ * transform, the scaling and the combine run once -- for binary splitting (T1 Q2 + P1 T2), the 2x2
+ * matrix products of a half-GCD, determinant and resultant steps.
+ * The pieces have bits1 = (N - depth - s) / 2 bits, s = ceil(log2 K): a coefficient of the summed
+ * convolutions is below K 2^depth (2^bits1 - 1)^2 < 2^N, so it is read off its residue as a single
+ * product's is (the multiply's own bits1 leaves no such room when N - depth is even).  The largest
+ * operands of a (depth, w) are therefore a few limbs smaller than the multiply's.
+ * The result has n1 + n2 + 1 limbs, the top one below K.  Operands are only read; pointers may
+ * repeat between terms and a_i == b_i is allowed; r overlaps no operand.
+ * Status: MPFFT_EINVAL for K outside [1, MPFFT_DOT_MAX] (and null pointers), MPFFT_ETOOBIG when
+ * j1 + j2 - 1 > 2^(depth+1) under that bits1, the rest as mpfft_check_params.  K = 1 is limb-equal
+ * to mpfft_mul_device with a zero top limb.
+ * Pointwise: the nested family accumulates inside its kernel (k_pwss for the first term, k_pwsa:
+ * C <- C + A B for the later ones); the other families form the product in place as the multiply
+ * does and add it with k_slotacc.  The workspace holds three coefficient arrays whatever K.
+ * Under mpfft_profile_begin/end every term claims a call slot (max_calls >= K per sum): the
+ * forward and pointwise stage times are sums over the terms, the returned call count counts terms.
+ * Not covered: signed terms (a b - c d), accumulating in the inner transform domain (one inner
+ * inverse for all terms), cached or shared forward transforms between terms (a 2x2 matrix
+ * product with eight forward transforms), squares as terms (a_i == b_i runs as a product), the
+ * sqrt2 front end, the mod 2^B +- 1 families, the sharded / multi-GPU entries and
+ * mpfft_set_devices routing. */
+#define MPFFT_DOT_MAX 64
+int mpfft_dot_check_params(long K, long n1, long n2, unsigned long depth, unsigned long w);
+/* out[10] as mpfft_plan_info */
+int mpfft_dot_plan_info(long K, long n1, long n2, unsigned long depth, unsigned long w, long *out);
+/* mpfft_choose's candidates and cost model under the dot bound */
+int mpfft_dot_choose(long K, long n1, long n2, unsigned long *depth, unsigned long *w);
+size_t mpfft_dot_workspace_bytes(long K, long n1, long n2, unsigned long depth, unsigned long w);   /* 0 on invalid parameters */
+/* out[11]: the eight entries of mpfft_workspace_layout, then the byte offsets of C's limb, top and
+ * carry-mask arrays. */
+int mpfft_dot_workspace_layout(long K, long n1, long n2, unsigned long depth, unsigned long w, size_t *out);
+/* d_a, d_b: host arrays of K device pointers (read during the call only).  Queued on `stream`, not
+ * synchronised. */
+int mpfft_dot_device(uint64_t *d_r, long K, const uint64_t *const *d_a, const uint64_t *const *d_b, long n1, long n2,
+                     unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* Host pointers: a, b arrays of K host operands; they go through the device context's buffers term
+ * by term.  mpfft_dot_auto: (depth, w) from mpfft_dot_choose. */
+int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
+                 unsigned long depth, unsigned long w);
+int mpfft_dot_auto(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2);
+/* As mpfft_stage_kernels; the pointwise field names the first term's kernel and the later terms':
+ * "k_pwss<M>... + k_pwsa<M>..." (with the pair / quad suffix) on nested plans, "<kernel> + k_slotacc"
+ * elsewhere. */
+int mpfft_dot_stage_kernels(long K, long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len);
+/* (tests) One MPFFT_STAGE_* stage for one term (d_a, d_b single operands) on the dot plan and
+ * workspace.  MPFFT_STAGE_POINTWISE writes C <- A B (A's arrays are overwritten); or-ed with
+ * MPFFT_STAGE_ACC it computes C <- C + A B (the nested family reads A and B only, the others
+ * overwrite A).  The stages behind the pointwise read C.  Like mpfft_stage it never fuses row
+ * levels.  MPFFT_STAGE_ACC on any other stage returns MPFFT_EINVAL. */
+#define MPFFT_STAGE_ACC 0x200
+int mpfft_dot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1, long n2,
+                    unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity

@@ -293,6 +293,30 @@ def lib():
             h.mpfft_mulmodw_choose.restype = ctypes.c_int
             h.mpfft_mulmodw_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
             h.mpfft_mulmodw_next_size.restype = ctypes.c_int
+        if hasattr(h, "mpfft_dot_device"):   # MPFFT_VERSION 8 (older libraries in A/B runs lack them)
+            _ulp = ctypes.POINTER(ctypes.c_ulong)
+            _sz = ctypes.c_size_t
+            _pp = ctypes.POINTER(ctypes.c_void_p)
+            h.mpfft_dot_check_params.argtypes = [_L, _L, _L, _UL, _UL]
+            h.mpfft_dot_check_params.restype = ctypes.c_int
+            h.mpfft_dot_plan_info.argtypes = [_L, _L, _L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
+            h.mpfft_dot_plan_info.restype = ctypes.c_int
+            h.mpfft_dot_choose.argtypes = [_L, _L, _L, _ulp, _ulp]
+            h.mpfft_dot_choose.restype = ctypes.c_int
+            h.mpfft_dot_workspace_bytes.argtypes = [_L, _L, _L, _UL, _UL]
+            h.mpfft_dot_workspace_bytes.restype = _sz
+            h.mpfft_dot_workspace_layout.argtypes = [_L, _L, _L, _UL, _UL, ctypes.POINTER(_sz)]
+            h.mpfft_dot_workspace_layout.restype = ctypes.c_int
+            h.mpfft_dot_device.argtypes = [_vp, _L, _pp, _pp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_dot_device.restype = ctypes.c_int
+            h.mpfft_dot_ex.argtypes = [_u64p, _L, _pp, _pp, _L, _L, _UL, _UL]
+            h.mpfft_dot_ex.restype = ctypes.c_int
+            h.mpfft_dot_auto.argtypes = [_u64p, _L, _pp, _pp, _L, _L]
+            h.mpfft_dot_auto.restype = ctypes.c_int
+            h.mpfft_dot_stage_kernels.argtypes = [_L, _L, _L, _UL, _UL, ctypes.c_char_p, _sz]
+            h.mpfft_dot_stage_kernels.restype = ctypes.c_int
+            h.mpfft_dot_stage.argtypes = [ctypes.c_int, _L, _vp, _vp, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_dot_stage.restype = ctypes.c_int
         _lib = h
     return _lib
 
@@ -606,6 +630,147 @@ def sqr_workspace_views(ws, n, depth, w):
     dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
     top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
     return dig, top
+
+
+# ---- sums of products (mpfft_dot_*, include/mpfft.h): r = sum_i a_i b_i with K forward transform
+# pairs and one inverse; the workspace has a third coefficient array C, the accumulator ----
+
+DOT_MAX = 64
+STAGE_ACC = 0x200   # dot_stage: or-ed onto STAGE_POINTWISE, C <- C + A B
+
+
+def dot_check_params(K, n1, n2, depth, w):
+    return lib().mpfft_dot_check_params(K, n1, n2, depth, w)
+
+
+def dot_plan_info(K, n1, n2, depth, w):
+    """plan_info of a K-term sum: bits1 = (N - depth - ceil(log2 K)) / 2 and what follows from it"""
+    out = (ctypes.c_long * 10)()
+    rc = lib().mpfft_dot_plan_info(K, n1, n2, depth, w, out)
+    if rc:
+        raise MpfftError(rc, f"dot plan(K={K}, n1={n1}, n2={n2}, depth={depth}, w={w})")
+    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
+    return dict(zip(keys, list(out)))
+
+
+def dot_choose(K, n1, n2):
+    """(depth, w) the library would use for a K-term sum of n1 x n2-limb products"""
+    d, w = ctypes.c_ulong(), ctypes.c_ulong()
+    rc = lib().mpfft_dot_choose(K, n1, n2, ctypes.byref(d), ctypes.byref(w))
+    if rc:
+        raise MpfftError(rc, f"dot_choose(K={K}, n1={n1}, n2={n2})")
+    return int(d.value), int(w.value)
+
+
+def dot_max_limbs(K, depth, w):
+    """largest n with n1 = n2 = n valid for a K-term sum at (depth, w): j1 = j2 = 2^depth pieces of
+    bits1 = (N - depth - ceil(log2 K)) / 2 bits"""
+    N = (1 << depth) * w
+    bits1 = (N - depth - (K - 1).bit_length()) // 2
+    return (1 << depth) * bits1 // 64
+
+
+def dot_workspace_bytes(K, n1, n2, depth, w):
+    return int(lib().mpfft_dot_workspace_bytes(K, n1, n2, depth, w))
+
+
+def alloc_workspace_dot(K, n1, n2, depth, w, device="cuda"):
+    import torch
+    nb = dot_workspace_bytes(K, n1, n2, depth, w)
+    if nb == 0:
+        raise MpfftError(dot_check_params(K, n1, n2, depth, w), "dot workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def dot_workspace_layout(K, n1, n2, depth, w):
+    out = (ctypes.c_size_t * 11)()
+    rc = lib().mpfft_dot_workspace_layout(K, n1, n2, depth, w, out)
+    if rc:
+        raise MpfftError(rc, "dot_workspace_layout")
+    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw", "digC", "topC", "cbC")
+    return dict(zip(keys, list(out)))
+
+
+def dot_workspace_views(ws, K, n1, n2, depth, w):
+    """{"A", "B", "C"} -> (dig, top, cb) views into a dot workspace tensor (slot-major): limbs
+    (slots, l) int64, carry limbs int32, carry-mask words (slots, cbw) int64"""
+    import torch
+    P = dot_plan_info(K, n1, n2, depth, w)
+    lay = dot_workspace_layout(K, n1, n2, depth, w)
+    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
+    u8 = ws.view(torch.uint8)
+
+    def arrays(x):
+        d, t, c = lay["dig" + x], lay["top" + x], lay["cb" + x]
+        return (u8[d:d + slots * l * 8].view(torch.int64).view(slots, l), u8[t:t + slots * 4].view(torch.int32),
+                u8[c:c + slots * cbw * 8].view(torch.int64).view(slots, cbw))
+    return {x: arrays(x) for x in "ABC"}
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def dot_device(d_r, d_as, d_bs, n1, n2, depth, w, ws, stream=None):
+    """d_r[:n1 + n2 + 1] = sum_i d_as[i][:n1] * d_bs[i][:n2], all tensors on the GPU (lists of K
+    tensors; the same tensor may appear more than once); queued on `stream`, not synchronised."""
+    if len(d_as) != len(d_bs):
+        raise ValueError("as many a_i as b_i")
+    rc = lib().mpfft_dot_device(_ptr(d_r), len(d_as), _ptr_array(d_as), _ptr_array(d_bs), n1, n2, depth, w, _ptr(ws),
+                                ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_dot_device")
+
+
+def _host_terms(a_list, b_list):
+    a_list = [np.ascontiguousarray(a, dtype=np.uint64) for a in a_list]
+    b_list = [np.ascontiguousarray(b, dtype=np.uint64) for b in b_list]
+    if len(a_list) != len(b_list) or not a_list:
+        raise ValueError("as many a_i as b_i, at least one")
+    n1, n2 = len(a_list[0]), len(b_list[0])
+    if any(len(a) != n1 for a in a_list) or any(len(b) != n2 for b in b_list):
+        raise ValueError("every a_i of n1 limbs, every b_i of n2 limbs")
+    pa = (ctypes.c_void_p * len(a_list))(*[a.ctypes.data for a in a_list])
+    pb = (ctypes.c_void_p * len(b_list))(*[b.ctypes.data for b in b_list])
+    return a_list, b_list, pa, pb, n1, n2
+
+
+def dot(a_list, b_list, depth, w):
+    """sum_i a_list[i] * b_list[i] as a new uint64 array of n1 + n2 + 1 limbs (host pointers, mpfft_dot_ex)"""
+    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
+    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
+    rc = lib().mpfft_dot_ex(_p(r), len(a_list), pa, pb, n1, n2, depth, w)
+    if rc:
+        raise MpfftError(rc, f"dot(K={len(a_list)}, n1={n1}, n2={n2}, depth={depth}, w={w})")
+    return r
+
+
+def dot_auto(a_list, b_list):
+    """dot() with (depth, w) from dot_choose()"""
+    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
+    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
+    rc = lib().mpfft_dot_auto(_p(r), len(a_list), pa, pb, n1, n2)
+    if rc:
+        raise MpfftError(rc, f"dot_auto(K={len(a_list)}, n1={n1}, n2={n2})")
+    return r
+
+
+def dot_stage(which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream=None):
+    """one stage for one term (d_a, d_b) on the K-term plan and workspace (tests)"""
+    rc = lib().mpfft_dot_stage(which, K, _ptr(d_a), _ptr(d_b), _ptr(d_r), n1, n2, depth, w, _ptr(ws),
+                               ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_dot_stage({which})")
+
+
+def dot_stage_kernels(K, n1, n2, depth, w):
+    """dict stage -> the kernels a K-term sum launches for it (the pointwise: the first term's kernel
+    + the later terms')"""
+    buf = ctypes.create_string_buffer(640)
+    rc = lib().mpfft_dot_stage_kernels(K, n1, n2, depth, w, buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_dot_stage_kernels")
+    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
 
 
 # ---- multiplication by a precomputed operand (mpfft_precomp_*, mpfft_mul_precomp_*, include/mpfft.h):

@@ -711,6 +711,63 @@ struct Exec {
         return launch(f, grid, dim3(P.tpb), lds, dig, cb, top, digB, topB, l, P.N);
     }
 
+    // ---- sums of products (make_plan_dot): the C arrays are the accumulator ------------------
+    // the row and column views' operand 0 from here on: the arrays of v's operand 0
+    void view_op0(const View &v)
+    {
+        row.dig[0] = col.dig[0] = v.dig[0];
+        row.cb[0] = col.cb[0] = v.cb[0];
+        row.top[0] = col.top[0] = v.top[0];
+    }
+
+    // C[slot] <- C[slot] + A[slot] over the live slots (k_slotacc, dot.hpp)
+    int slot_acc(long cnt)
+    {
+        void (*f)(u64 *, u64 *, int *, const u64 *, const u64 *, const int *, int) = nullptr;
+        switch (P.U) {
+        case 1: f = k_slotacc<1>; break;
+        case 2: f = k_slotacc<2>; break;
+        case 4: f = k_slotacc<4>; break;
+        }
+        if (!f) return MPFFT_EUNSUPPORTED;
+        return launch(f, dim3((unsigned)cnt), dim3(P.tpb), lds_bytes((int)P.l, 0, 1, P.U, nw), cview.dig[0], cview.cb[0],
+                      cview.top[0], (const u64 *)row.dig[0], (const u64 *)row.cb[0], (const int *)row.top[0], (int)P.l);
+    }
+
+    // one term's pointwise, the views on that term's transformed operands.
+    // acc: C <- C + A B: k_pwsa on nested plans (A and B only read), else the product in place in A
+    // as pointwise() forms it and k_slotacc behind it.
+    // !acc (the first term): pointwise() as it stands -- the fused k_pwss writes C; the kernels that
+    // work in place leave the product in the views' operand 0, which the caller has pointed at C
+    // (run_dot) or copies there (the stage entry).
+    int pointwise_dot(bool acc)
+    {
+        const long cnt = (long)rcount * P.NC;
+        if (cnt == 0 || !cview.dig[0]) return MPFFT_EINVAL;
+        if (!acc) return pointwise();
+        if (!pwss_active()) {
+            int rc = pointwise();
+            return rc ? rc : slot_acc(cnt);
+        }
+        const int lk = pwss_lk_of(P.l), M = pw_inner_limbs(P.l, lk), fz = row_fused();
+        pw_acc_fn f = pw_get_acc(M, lk, fz);
+        if (!f) return MPFFT_EUNSUPPORTED;   // a missing accumulating instance is an error
+        return launch(f, dim3((unsigned)cnt), dim3(1u << lk), pw_lds(M, 1 << lk, (int)P.l), (const u64 *)row.dig[0],
+                      (const u64 *)row.cb[0], (const int *)row.top[0], (const u64 *)row.dig[1], (const u64 *)row.cb[1],
+                      (const int *)row.top[1], (int)P.l, cview.dig[0], cview.cb[0], cview.top[0],
+                      (unsigned long long *)nullptr);
+    }
+
+    // the live slots of the views' operand 0 -> C (the stage entry's first term on the in-place kernels)
+    int copy_to_c()
+    {
+        const size_t cnt = (size_t)rcount * P.NC;
+        HIPCHK(hipMemcpyAsync(cview.dig[0], row.dig[0], cnt * P.l * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(cview.cb[0], row.cb[0], cnt * cb_words((int)P.l) * 8, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(cview.top[0], row.top[0], cnt * 4, hipMemcpyDeviceToDevice, s));
+        return MPFFT_OK;
+    }
+
     // stage 4: row DIT inverse, MFA un-twiddle at the end
     int inv_rows()
     {

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "dot.hpp"
 #include "combine.hpp"
 #include "fold.hpp"
 #include "nega.hpp"
@@ -298,6 +299,58 @@ static int run_all_mod(const Plan &P, u64 *d_r, const u64 *d_a, const u64 *d_b, 
     return rc;
 }
 
+// The sum of K products on a make_plan_dot plan: per term the multiply's forward columns and rows of
+// (a_i, b_i) and the pointwise into the C arrays -- the first term writes them, the later ones add
+// to them (Exec::pointwise_dot) -- then the multiply's inverse rows, inverse columns, scaling and
+// combine once, on C, for n1 + n2 + 1 limbs.  Where the pointwise works in place (every plan that
+// fuses no row level), the first term's operand 0 is transformed in the C arrays themselves, so its
+// product lands in C without a copy.  term(i, &a, &b): the device operands of term i (the host
+// entries queue their copies there).
+// Profiling: every term claims a call slot and marks its forward columns, rows and pointwise; the
+// last term's slot carries the inverse side, the others mark those boundaries at once (empty
+// stages) -- mpfft_profile_end's sums are the sum's stage times, its call count the terms.
+template <typename Term>
+static int run_dot(const Plan &P, long K, u64 *d_r, unsigned char *ws, hipStream_t s, Term term)
+{
+    Exec X(P, s);
+    X.single(ws);
+    X.zflags = X.comb_flags(ws);
+    X.zflags_n = X.comb_flag_words(P, P.total);
+    X.drive_single();
+    X.fuse_row_last = true;
+    const View ab = X.col;
+    const bool in_place = X.row_fused() == 0;
+    int rc = MPFFT_OK;
+    for (long i = 0; i < K; ++i) {
+        const u64 *a = nullptr, *b = nullptr;
+        ProfCall pc;
+        pc.mark(0, s);
+        if ((rc = term(i, &a, &b))) return rc;
+        X.col = X.row = ab;
+        if (i == 0 && in_place) X.view_op0(X.cview);
+        if ((rc = X.fwd_columns(a, P.n1, b, P.n2, 2))) return rc;
+        pc.mark(1, s);
+        if ((rc = X.fwd_rows(2))) return rc;
+        pc.mark(2, s);
+        if ((rc = X.pointwise_dot(i > 0))) return rc;
+        pc.mark(3, s);
+        if (i + 1 < K) {
+            for (int k = 4; k <= MPFFT_NSTAGES; ++k) pc.mark(k, s);
+            continue;
+        }
+        X.view_op0(X.cview);
+        if ((rc = X.inv_rows())) return rc;
+        pc.mark(4, s);
+        if ((rc = X.itft(0, P.NR, P.Tr))) return rc;
+        pc.mark(5, s);
+        if ((rc = X.scale())) return rc;
+        pc.mark(6, s);
+        rc = X.fold ? X.combine_fold(d_r, ws, X.dbl_lo, X.dbl_hi) : X.combine_single(d_r, ws);
+        pc.mark(7, s);
+    }
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -341,7 +394,7 @@ static std::string stage_kernel_names(const Plan &P)
     if (fam == PWF_NESTED) {
         const int lk = pwss_lk_of(P.l);
         const char *fz = diag_env("MPFFT_FUSE_ROW");
-        const bool fused = P.has_c && !(fz && !strcmp(fz, "0"));   // as Exec::row_fused() in run_all
+        const bool fused = P.fuse_rows > 0 && !(fz && !strcmp(fz, "0"));   // as Exec::row_fused() in run_all
         snprintf(pw, sizeof pw, "%s<%d>%s (nested negacyclic, K=%d)", P.sqr ? "k_pwsq" : P.pre ? "k_pwsp" : "k_pwss", pw_inner_limbs(P.l, lk),
                  !fused ? "" : P.fuse_rows == 2 ? " quad + last two row levels" : " pair + last row level", 1 << lk);
     } else {
@@ -424,7 +477,7 @@ static void layout_out(const Plan &P, size_t *out)
 // One single-GPU stage (device pointers) on plan P; `ws` has P's workspace layout.  A squaring
 // plan's forward stages run operand 0 alone.
 static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const uint64_t *d_i2, uint64_t *d_r,
-                        void *d_ws, size_t ws_bytes, void *stream, const void *d_pre = nullptr)
+                        void *d_ws, size_t ws_bytes, void *stream, const void *d_pre = nullptr, bool from_c = false)
 {
     const bool driven = (stage & MPFFT_STAGE_DRIVEN) != 0;   // (tests) the inverse stages as run_all drives them
     stage &= ~MPFFT_STAGE_DRIVEN;
@@ -435,6 +488,7 @@ static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const ui
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
     X.use_pre(d_pre);
+    if (from_c) X.view_op0(X.cview);   // a dot plan's stages behind the pointwise: the accumulator
     if (driven) {
         X.drive_single();
         if (stage == MPFFT_STAGE_SCALE) plan_dbl(P, &X.dbl_lo, &X.dbl_hi);
@@ -1612,6 +1666,164 @@ int mpfft_mulmodm1_next_size(long min_L, long *L, unsigned long *depth, unsigned
 {
     if (min_L < 1) return MPFFT_EINVAL;
     return cyc_pick(0, min_L, L, depth, w);
+}
+
+// ---- sums of products (mpfft_dot_*, MPFFT_VERSION 8) -----------------------------------------
+int mpfft_dot_check_params(long K, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_dot(&P, K, n1, n2, depth, w);
+}
+
+int mpfft_dot_plan_info(long K, long n1, long n2, unsigned long depth, unsigned long w, long *out)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    plan_info_out(P, out);
+    return MPFFT_OK;
+}
+
+size_t mpfft_dot_workspace_bytes(long K, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan_dot(&P, K, n1, n2, depth, w)) return 0;
+    return P.bytes;
+}
+
+int mpfft_dot_workspace_layout(long K, long n1, long n2, unsigned long depth, unsigned long w, size_t *out)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    layout_out(P, out);
+    out[8] = P.off_digC; out[9] = P.off_topC; out[10] = P.off_cbC;
+    return MPFFT_OK;
+}
+
+int mpfft_dot_choose(long K, long n1, long n2, unsigned long *depth, unsigned long *w)
+{
+    if (K < 1 || K > DOT_MAX) return MPFFT_EINVAL;
+    double best = -1.0;
+    for (unsigned long d = 2; d <= 24; ++d)
+        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
+            const unsigned long long N = (1ull << d) * wv;
+            if (N % 64) continue;
+            if (N / 64 > 4096) break;
+            Plan P;
+            if (make_plan_dot(&P, K, n1, n2, d, wv)) continue;
+            const double c = choose_cost(P);
+            if (best < 0 || c < best) {
+                best = c;
+                *depth = d;
+                *w = wv;
+            }
+        }
+    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+}
+
+int mpfft_dot_device(uint64_t *d_r, long K, const uint64_t *const *d_a, const uint64_t *const *d_b, long n1, long n2,
+                     unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!d_r || !d_a || !d_b) return MPFFT_EINVAL;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    return run_dot(P, K, d_r, (unsigned char *)d_ws, (hipStream_t)stream, [&](long i, const u64 **a, const u64 **b) {
+        *a = d_a[i];
+        *b = d_b[i];
+        return *a && *b ? MPFFT_OK : MPFFT_EINVAL;
+    });
+}
+
+// The pointwise field of a dot plan: what the first term runs + what the later terms run
+int mpfft_dot_stage_kernels(long K, long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    std::string names = stage_kernel_names(P);
+    size_t f0 = 0;   // the third of the seven ';'-joined fields
+    for (int k = 0; k < 2; ++k) f0 = names.find(';', f0) + 1;
+    const size_t f1 = names.find(';', f0);
+    std::string pw = names.substr(f0, f1 - f0);
+    if (pw_family(P) == PWF_NESTED) {
+        std::string acc = pw;
+        acc.replace(acc.find("k_pwss"), 6, "k_pwsa");
+        pw += " + " + acc;
+    } else {
+        pw += " + k_slotacc";
+    }
+    names.replace(f0, f1 - f0, pw);
+    return copy_out(names, buf, len);
+}
+
+int mpfft_dot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1, long n2,
+                    unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    const bool acc = (stage & MPFFT_STAGE_ACC) != 0;
+    stage &= ~MPFFT_STAGE_ACC;
+    if (acc && stage != MPFFT_STAGE_POINTWISE) return MPFFT_EINVAL;
+    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (stage == MPFFT_STAGE_POINTWISE) {
+        (void)hipGetLastError();
+        Exec X(P, (hipStream_t)stream);
+        X.single((unsigned char *)d_ws);
+        if (acc) return X.pointwise_dot(true);
+        if ((rc = X.pointwise_dot(false))) return rc;
+        return X.copy_to_c();   // (no row level is fused here: the product was formed in place in A)
+    }
+    if (stage == MPFFT_STAGE_FWD_COLUMNS || stage == MPFFT_STAGE_FWD_ROWS)
+        return single_stage(P, stage, d_a, d_b, d_r, d_ws, ws_bytes, stream);
+    return single_stage(P, stage, d_a, d_b, d_r, d_ws, ws_bytes, stream, nullptr, true);   // the inverse side reads C
+}
+
+// Host operands: the context's io buffer holds one term's operands and, behind them, the sum; each
+// term's copies are queued on the context's stream in front of its forward passes.
+int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
+                 unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!r || !a || !b) return MPFFT_EINVAL;
+    DevCtx *C;
+    int dev = 0;
+    if ((rc = host_ctx(&C, &dev))) return rc;
+    std::lock_guard<std::mutex> lk(C->mu);
+    if (!C->stream) HIPCHK(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking));
+    if ((rc = ensure_buf((void **)&C->ws, &C->ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C->io, &C->io_bytes, (size_t)(n1 + n2 + P.total) * 8))) return rc;
+    u64 *d_a = C->io, *d_b = d_a + n1, *d_r = d_b + n2;
+    hipStream_t s = C->stream;
+    rc = run_dot(P, K, d_r, C->ws, s, [&](long i, const u64 **pa, const u64 **pb) {
+        if (!a[i] || !b[i]) return (int)MPFFT_EINVAL;
+        HIPCHK(hipMemcpyAsync(d_a, a[i], (size_t)n1 * 8, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_b, b[i], (size_t)n2 * 8, hipMemcpyHostToDevice, s));
+        *pa = d_a;
+        *pb = d_b;
+        return (int)MPFFT_OK;
+    });
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(r, d_r, (size_t)P.total * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MPFFT_OK;
+}
+
+int mpfft_dot_auto(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2)
+{
+    unsigned long d = 0, wv = 0;
+    const int rc = mpfft_dot_choose(K, n1, n2, &d, &wv);
+    if (rc) return rc;
+    return mpfft_dot_ex(r, K, a, b, n1, n2, d, wv);
 }
 
 // release the calling device's cached workspace (the next call re-allocates)

@@ -13,6 +13,12 @@ typedef void (*pw_fn)(uint64_t *, uint64_t *, int *, const uint64_t *, const uin
 pw_fn pw_get(int M, int lk, int fuse = 0);
 size_t pw_lds(int M, int K, int l);
 
+// k_pwsa<M, lk, fuse> (pwsa.hip): the accumulating form, C[slot] <- C[slot] + A[slot] B[slot] at every
+// fuse (A and B only read), the same instances, LDS and launch shape as k_pwss; nullptr if not built
+typedef void (*pw_acc_fn)(const uint64_t *, const uint64_t *, const int *, const uint64_t *, const uint64_t *, const int *,
+                          int, uint64_t *, uint64_t *, int *, unsigned long long *);
+pw_acc_fn pw_get_acc(int M, int lk, int fuse = 0);
+
 // k_pwsq<M, lk, fuse>: the squaring form (A <- A^2, no operand B), the same instances, LDS and
 // launch shape as k_pwss; nullptr if not built
 typedef void (*pw_sq_fn)(uint64_t *, uint64_t *, int *, int, uint64_t *, uint64_t *, int *, unsigned long long *);

@@ -1180,7 +1180,12 @@ __device__ __forceinline__ void pw_slot_product(u64 (&La)[M], int Ta, u64 (&Lb)[
 // (pa, cbp, *topp).  c_t 2^(Bt) = v_t 2^(Bt) - s_t (2^(Bt) + 2^(N' + Bt)); positions >= N
 // wrap negated.  Thread t of NTH sums output limbs m = t + NTH r (coalesced, consecutive
 // per wave).  H (the l limb overflows) aliases X: written after a barrier.
-template <int M, int LK, int NTH = (1 << LK)>
+// ACC (k_pwsa): the slot's previous value at (pa, cbp, *topp) is added: limb m of it, and the +-1
+// carry out of limb m - 1 its mask words hold, enter limb m's sum; its top and the carry out of
+// limb l - 1 weigh 2^N == -1 and enter limb 0 negated.  All of it is read in the summing loop, before
+// the barriers in front of the first store, so the slot is updated in place; the output is the same
+// reduced form.  (Requesting the old limbs ahead of the loop spilled 8 bytes at M = 18.)
+template <int M, int LK, int NTH = (1 << LK), bool ACC = false>
 __device__ __forceinline__ void pw_slot_output(const u64 *X, const int *TT, int *H, u64 *pa, u64 *cbp, int *topp, int l,
                                                int t)
 {
@@ -1197,6 +1202,12 @@ __device__ __forceinline__ void pw_slot_output(const u64 *X, const int *TT, int 
         if (r >= RPT) continue;
         const int m = t + NTH * r;
         i128 S = 0;
+        if constexpr (ACC) {
+            const int q = m ? m - 1 : l - 1;
+            const u64 pw = cbp[2 * (q >> 6)], nw = cbp[2 * (q >> 6) + 1];
+            const int cin = (int)((pw >> (q & 63)) & 1) - (int)((nw >> (q & 63)) & 1);
+            S = (i128)pa[m] + (m ? cin : -(cin + *topp));
+        }
         // limb d of c_tp (0 .. M): two's complement in the tight form (limb M the sign extension)
         auto limb_of = [&](int d, int tp) -> i128 {
             i128 v;
@@ -1295,10 +1306,21 @@ __device__ __forceinline__ long pw_fused_slot(long b, long nb)
 // on one XCD.
 // (Fusing the inverse row DIT's first level as well needs both products in one workgroup:
 // measured at 194-256 VGPRs, occupancy 2 -> 1, so the inverse side stays a pass.)
-template <int M, int LK, int FUSE>
-__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<M, LK>()))) void k_pwss(u64 *digA, u64 *cbA, int *topA, const u64 *digB, const u64 *cbB,
-                                                  const int *topB, int l, u64 *digC, u64 *cbC, int *topC,
-                                                  unsigned long long *dbg)
+// The kernel's body is pw_mul_slot, shared with the accumulating k_pwsa below.
+
+// the slot's output at `slot` of the arrays (dig, cb, top); ACC: added to what is there
+template <int M, int LK, bool ACC>
+__device__ __forceinline__ void pw_slot_store(const u64 *X, const int *TT, int *H, u64 *dig, u64 *cb, int *top, long slot,
+                                              int l, int cbw, int t)
+{
+    pw_slot_output<M, LK, (1 << LK), ACC>(X, TT, H, dig + (size_t)slot * l, cb + (size_t)slot * cbw, top + slot, l, t);
+}
+
+// the workgroup of k_pwss (ACC false) and of k_pwsa (ACC true: the product is added to C[slot], at every FUSE)
+template <int M, int LK, int FUSE, bool ACC>
+__device__ __forceinline__ void pw_mul_slot(u64 *digA, u64 *cbA, int *topA, const u64 *digB, const u64 *cbB,
+                                            const int *topB, int l, u64 *digC, u64 *cbC, int *topC,
+                                            unsigned long long *dbg)
 {
     // diagnostics (MPFFT_PW_STAMPS): thread 0 stamps the phase boundaries of this workgroup
     unsigned long long *stamp = dbg ? dbg + 8 * (size_t)blockIdx.x : nullptr;
@@ -1320,7 +1342,7 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp, loadB);
         // every piece of A was read before the first barrier of A's transform: the output may
         // overwrite A in place
-        pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
+        pw_slot_store<M, LK, ACC>(X, TT, H, ACC ? digC : digA, ACC ? cbC : cbA, ACC ? topC : topA, slot, l, cbw, t);
     } else if (FUSE == 0) {
         const long slot = blockIdx.x;
         {
@@ -1332,7 +1354,7 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         }
         __syncthreads();   // every piece read before any output limb is written (in place on A)
         pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp);
-        pw_slot_output<M, LK>(X, TT, H, digA + (size_t)slot * l, cbA + (size_t)slot * cbw, topA + slot, l, t);
+        pw_slot_store<M, LK, ACC>(X, TT, H, ACC ? digC : digA, ACC ? cbC : cbA, ACC ? topC : topA, slot, l, cbw, t);
     } else if (FUSE == 2) {
         // the row DIF's last two levels on load, slot quads
         const long slot = pw_fused_slot<2>(blockIdx.x, gridDim.x);
@@ -1350,7 +1372,7 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
             pw_load_quad_bfly<M, CLP, K>(Lb, Tb, digB, cbB, topB, s0, pos, l, cbw, t);
             pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp);
         }
-        pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
+        pw_slot_store<M, LK, ACC>(X, TT, H, digC, cbC, topC, slot, l, cbw, t);
     } else {
         const long slot = pw_fused_slot<1>(blockIdx.x, gridDim.x);
         pw_load_pair_bfly<M, CLP>(La, Ta, digA, cbA, topA, slot & ~1L, l, cbw, t, slot & 1);
@@ -1363,12 +1385,31 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
             pw_load_pair_bfly<M, CLP>(Lb, Tb, digB, cbB, topB, slot & ~1L, l, cbw, t, slot & 1);
             pw_slot_product<M, LK>(La, Ta, Lb, Tb, X, Xw, TT, t, stamp);
         }
-        pw_slot_output<M, LK>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
+        pw_slot_store<M, LK, ACC>(X, TT, H, digC, cbC, topC, slot, l, cbw, t);
     }
     if (stamp) {
         __syncthreads();
         if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();
     }
+}
+
+template <int M, int LK, int FUSE>
+__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<M, LK>()))) void k_pwss(u64 *digA, u64 *cbA, int *topA, const u64 *digB, const u64 *cbB,
+                                                  const int *topB, int l, u64 *digC, u64 *cbC, int *topC,
+                                                  unsigned long long *dbg)
+{
+    pw_mul_slot<M, LK, FUSE, false>(digA, cbA, topA, digB, cbB, topB, l, digC, cbC, topC, dbg);
+}
+
+// k_pwsa<M, LK, FUSE>: C[slot] <- C[slot] + A[slot] * B[slot] mod 2^N + 1 (the sums of products,
+// mpfft_dot_*): k_pwss with its loaders for that FUSE and the accumulating pw_slot_output.  A and B
+// are only read, at FUSE 0 as well.
+template <int M, int LK, int FUSE>
+__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<M, LK>()))) void k_pwsa(const u64 *digA, const u64 *cbA, const int *topA, const u64 *digB, const u64 *cbB,
+                                                  const int *topB, int l, u64 *digC, u64 *cbC, int *topC,
+                                                  unsigned long long *dbg)
+{
+    pw_mul_slot<M, LK, FUSE, true>((u64 *)digA, (u64 *)cbA, (int *)topA, digB, cbB, topB, l, digC, cbC, topC, dbg);
 }
 
 // ---------------------------------------------------------------------------

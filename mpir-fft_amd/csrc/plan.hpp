@@ -148,8 +148,9 @@ static PwFamily pw_family(const Plan &P)
 // sqrt2: the new_mpn_mul6 front end (mul_fft.c:3573-3603): a length-4n convolution with
 // bits1 = (N - (depth + 1))/2 (:3578) and the same trunc rule (:3603)
 // lbc >= 0: NC = 2^lbc instead of the reference's split; fwd4: four-level forward k_rpass passes
+// sbits: bits of headroom the coefficients keep for a sum of up to 2^sbits products (make_plan_dot)
 static int make_plan_split(Plan *p, long n1, long n2, unsigned long depth, unsigned long w, bool sqrt2, int lbc,
-                           bool fwd4 = false)
+                           bool fwd4 = false, int sbits = 0)
 {
     memset(p, 0, sizeof(*p));
     p->sqrt2 = sqrt2;
@@ -165,7 +166,8 @@ static int make_plan_split(Plan *p, long n1, long n2, unsigned long depth, unsig
     p->l = (long)(p->N / 64);
     if (p->N <= depth) return MPFFT_EINVAL;
     if (sqrt2 && p->N <= depth + 1) return MPFFT_EINVAL;
-    p->bits1 = (p->N - depth - (sqrt2 ? 1 : 0)) / 2;
+    if (p->N <= depth + (u64)sbits) return MPFFT_EINVAL;
+    p->bits1 = (p->N - depth - (sqrt2 ? 1 : 0) - (u64)sbits) / 2;
     if (p->bits1 < 1) return MPFFT_EINVAL;
     p->NC = 1L << (lbc >= 0 ? lbc : (int)depth / 2);   // the reference's split (mul_fft.c:3195) unless make_plan picks another
     p->NR = 2 * p->n / p->NC;
@@ -314,9 +316,9 @@ static void plan_dbl(const Plan &P, long *lo, long *hi)
 // half and wins (C2: 6.69 vs 6.99 ms); at l = 4096 (C4) 512 x 512 with three-level passes
 // measured slower (97.1 vs 96.2 ms).  profiles/r04/mfa_split_ab.txt.  Both splits give the
 // same exact product.
-static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned long w, bool sqrt2 = false)
+static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned long w, bool sqrt2 = false, int sbits = 0)
 {
-    int rc = make_plan_split(p, n1, n2, depth, w, sqrt2, -1);
+    int rc = make_plan_split(p, n1, n2, depth, w, sqrt2, -1, false, sbits);
     // diagnostics (A/B): MPFFT_SPLIT=ref / alt forces a split
     static const char *force = diag_env("MPFFT_SPLIT");
     // l = 4096, truncation case b: twice the reference's columns since the live-group launches (C4 74.1-74.3
@@ -324,7 +326,7 @@ static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned lo
     if (!rc && !sqrt2 && p->rpass && p->l == 4096 && !(force && !strcmp(force, "ref"))
         && (2 * p->Tr > p->NR || (force && !strcmp(force, "alt4")))) {
         Plan q;
-        if (make_plan_split(&q, n1, n2, depth, w, sqrt2, (int)depth / 2 + 1) == MPFFT_OK && q.rpass) *p = q;
+        if (make_plan_split(&q, n1, n2, depth, w, sqrt2, (int)depth / 2 + 1, false, sbits) == MPFFT_OK && q.rpass) *p = q;
         return rc;
     }
     if (rc || sqrt2 || !p->rpass || p->l != 2048 || (force && !strcmp(force, "ref"))) return rc;
@@ -334,7 +336,7 @@ static int make_plan(Plan *p, long n1, long n2, unsigned long depth, unsigned lo
     const bool casea = 2 * p->Tr <= p->NR;
     if (!(force && !strcmp(force, "alt")) && casea && (depth < 13 || depth > 15)) return rc;
     Plan q;
-    if (make_plan_split(&q, n1, n2, depth, w, sqrt2, (int)depth / 2 + 1, true) == MPFFT_OK && q.rpass
+    if (make_plan_split(&q, n1, n2, depth, w, sqrt2, (int)depth / 2 + 1, true, sbits) == MPFFT_OK && q.rpass
         && (!casea || (force && !strcmp(force, "alt")) || q.trunc <= p->trunc + p->trunc / 64))   // case a: at most 1/64 more truncated length
         *p = q;
     return MPFFT_OK;
@@ -357,6 +359,39 @@ static void plan_drop_b(Plan *p, bool sqr = true)
     p->off_flags -= b;
     p->off_meta -= b;
     p->bytes -= b;
+}
+
+// Sum of K products (mpfft_dot_*): r = sum_{i < K} a_i b_i, every a_i of n1 and every b_i of n2 limbs.
+// The multiply's planner with bits1 = (N - depth - s) / 2, s = ceil(log2 K): a coefficient of the summed
+// convolutions is c_k <= K min(j1, j2) (2^bits1 - 1)^2 < 2^(s + depth + 2 bits1) <= 2^N (min(j1, j2) <=
+// n = 2^depth since j1 + j2 - 1 <= 2n), so the sum is read off the residues mod 2^N + 1 as one product
+// is -- the multiply's own bits1 leaves no such room when N - depth is even.  j1, j2, trunc, the split,
+// fold, ltw and fuse_rows follow from that bits1 as the multiply's do.  The sum has n1 + n2 + 1 limbs
+// (the top one below K), and every dot plan has the C arrays: the accumulator.  K = 1 is the
+// multiply's plan apart from those two.
+static const int DOT_MAX = 64;
+static int dot_sbits(long K) { return ilog2(K); }
+static int make_plan_dot(Plan *p, long K, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    if (K < 1 || K > DOT_MAX) {
+        memset(p, 0, sizeof(*p));
+        return MPFFT_EINVAL;
+    }
+    const int rc = make_plan(p, n1, n2, depth, w, false, dot_sbits(K));
+    if (rc) return rc;
+    p->total = n1 + n2 + 1;
+    // the regions behind B again: C, the combine flags for `total` limbs, the fold's meta words
+    size_t o = p->has_c ? p->off_digC : p->off_flags;
+    const size_t dig = p->slots * p->l * 8, top = align_up(p->slots * 4, 256);
+    const size_t cbb = align_up(p->slots * cb_words((int)p->l) * 8, 256);
+    p->has_c = true;
+    p->off_digC = o; o += dig;
+    p->off_topC = o; o += top;
+    p->off_cbC = o; o += cbb;
+    p->off_flags = o; o += align_up((size_t)(p->total / 256 + 8) * 4, 256);
+    p->off_meta = o; o += align_up((size_t)p->slots * 4, 256);
+    p->bytes = o;
+    return MPFFT_OK;
 }
 
 // Squaring plan: the multiply's plan for n by n limbs -- the same split, trunc, fold, ltw and
