@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 8
+#define MPFFT_VERSION 9
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -338,7 +338,8 @@ int mpfft_mulmodw_next_size(long min_L, long *L, unsigned long *depth, unsigned 
  * does and add it with k_slotacc.  The workspace holds three coefficient arrays whatever K.
  * Under mpfft_profile_begin/end every term claims a call slot (max_calls >= K per sum): the
  * forward and pointwise stage times are sums over the terms, the returned call count counts terms.
- * Not covered: signed terms (a b - c d), accumulating in the inner transform domain (one inner
+ * Signed terms (a b - c d) are the mpfft_sdot_* entries below.
+ * Not covered: accumulating in the inner transform domain (one inner
  * inverse for all terms), cached or shared forward transforms between terms (a 2x2 matrix
  * product with eight forward transforms), squares as terms (a_i == b_i runs as a product), the
  * sqrt2 front end, the mod 2^B +- 1 families, the sharded / multi-GPU entries and
@@ -374,6 +375,62 @@ int mpfft_dot_stage_kernels(long K, long n1, long n2, unsigned long depth, unsig
 #define MPFFT_STAGE_ACC 0x200
 int mpfft_dot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1, long n2,
                     unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---- signed sums of products (MPFFT_VERSION 9): r[0 .. n1 + n2 + 1) = sum_{i < K} s_i a_i b_i, s_i = -1
+ * where bit i of `neg` is set and +1 elsewhere -- determinants (a d - b c), a half-GCD matrix applied
+ * to a vector, CRT recombinations, resultant steps, Newton residuals (1 - x d) -- on the plan, the
+ * (depth, w) validity, the operand bound and the chooser of mpfft_dot_* (use mpfft_dot_choose and
+ * mpfft_dot_plan_info), with K forward transform pairs and one inverse.
+ * Exact, no bit of headroom lost: with X = 2^(64 n1), a term that is subtracted feeds the transforms
+ * the limb-wise complement ~a_i = X - 1 - a_i (n1 limbs, non-negative, the same number of pieces), so
+ * the unsigned sum comes out as r' = r + (X - 1) D, D = sum_neg b_i (at most n2 + 1 limbs), and
+ * r = r' - X D + D mod 2^(64 (n1 + n2 + 1)).  Every piece stays in [0, 2^bits1) and every coefficient
+ * below 2^N under the dot plan's bits1; the transform, pointwise, accumulate, inverse and combine
+ * kernels run as they do for mpfft_dot_*.  Two streaming steps are added: per negative term k_sdneg
+ * (~a_i into a scratch the split reads, D <- D + b_i in carry-save form, the first negative term
+ * initialising D) and, once behind the combine, d_r <- d_r + D - (D << 64 n1) in place (k_sdedge +
+ * k_sdfix: the reduced-form combine's signed carry chain over blocks of MPFFT_SDOT_FIX_BLOCK limbs).
+ * A fixed number of launches per sum, no host synchronisation; neg == 0 launches neither and is
+ * limb-equal to mpfft_dot_*.
+ * Result: n1 + n2 + 1 limbs, the two's-complement value of the signed sum (|r| < 64 2^(64 (n1 + n2)));
+ * the sign is bit 63 of the top limb, which lies in [0, K) or [2^64 - K, 2^64).  Operands are only
+ * read; pointers may repeat between terms, whatever their signs, and a_i == b_i is allowed; r
+ * overlaps no operand.
+ * Status: MPFFT_EINVAL if `neg` has a bit at or above K, everything else as mpfft_dot_check_params; a
+ * workspace that is too small returns MPFFT_ENOMEM.
+ * Workspace: the dot workspace followed by the complement scratch (8 n1 bytes) and D, every offset
+ * 256-byte aligned; its size does not depend on `neg`, it need not be cleared, and a dot workspace laid
+ * at its front is valid for mpfft_dot_stage.
+ * Under mpfft_profile_begin/end the pre-pass counts with its term's forward-columns stage and the
+ * correction with the combine stage; call slots stay one per term.
+ * Not covered: the complement fused into the split loads (it would save the scratch's round trip,
+ * 16 n1 bytes per negative term), the correction fused into the combine (16 (n1 + n2 + 1) bytes per
+ * sum), signed terms on the mod 2^B +- 1 families, the sqrt2 front end, the sharded / multi-GPU
+ * entries and mpfft_set_devices routing, shared forward transforms between terms. */
+#define MPFFT_SDOT_FIX_BLOCK 4096   /* limbs per block of the correction's carry chain */
+int mpfft_sdot_check_params(long K, uint64_t neg, long n1, long n2, unsigned long depth, unsigned long w);
+size_t mpfft_sdot_workspace_bytes(long K, long n1, long n2, unsigned long depth, unsigned long w);   /* 0 on invalid parameters */
+/* out[13]: the eleven entries of mpfft_dot_workspace_layout, then the byte offsets of the complement
+ * scratch (n1 limbs) and of D (n2 limbs, behind them one overflow byte per limb). */
+int mpfft_sdot_workspace_layout(long K, long n1, long n2, unsigned long depth, unsigned long w, size_t *out);
+/* As mpfft_dot_device; d_ws holds mpfft_sdot_workspace_bytes bytes. */
+int mpfft_sdot_device(uint64_t *d_r, long K, uint64_t neg, const uint64_t *const *d_a, const uint64_t *const *d_b,
+                      long n1, long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* Host pointers, term by term through the device context's buffers as mpfft_dot_ex (D lives on the
+ * device: no operand is kept after its term).  mpfft_sdot_auto: (depth, w) from mpfft_dot_choose. */
+int mpfft_sdot_ex(uint64_t *r, long K, uint64_t neg, const uint64_t *const *a, const uint64_t *const *b,
+                  long n1, long n2, unsigned long depth, unsigned long w);
+int mpfft_sdot_auto(uint64_t *r, long K, uint64_t neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2);
+/* mpfft_dot_stage_kernels' seven fields; when neg != 0 the fwd_columns field is prefixed by
+ * "k_sdneg + " and the combine field suffixed by " + k_sdedge + k_sdfix (blocks of 4096 limbs)". */
+int mpfft_sdot_stage_kernels(long K, uint64_t neg, long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len);
+/* (tests) The two stages of this family on its workspace; every other stage is forwarded to
+ * mpfft_dot_stage on the same workspace.  MPFFT_STAGE_ACC on anything but MPFFT_STAGE_POINTWISE and
+ * MPFFT_STAGE_SD_NEG returns MPFFT_EINVAL. */
+#define MPFFT_STAGE_SD_NEG 10   /* d_a -> complement scratch, D <- d_b; or-ed with MPFFT_STAGE_ACC: D <- D + d_b */
+#define MPFFT_STAGE_SD_FIX 11   /* d_r <- d_r + D - (D << 64 n1), n1 + n2 + 1 limbs */
+int mpfft_sdot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1, long n2,
+                     unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity

@@ -317,6 +317,26 @@ def lib():
             h.mpfft_dot_stage_kernels.restype = ctypes.c_int
             h.mpfft_dot_stage.argtypes = [ctypes.c_int, _L, _vp, _vp, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
             h.mpfft_dot_stage.restype = ctypes.c_int
+        if hasattr(h, "mpfft_sdot_device"):   # MPFFT_VERSION 9
+            _sz = ctypes.c_size_t
+            _pp = ctypes.POINTER(ctypes.c_void_p)
+            _U64 = ctypes.c_uint64
+            h.mpfft_sdot_check_params.argtypes = [_L, _U64, _L, _L, _UL, _UL]
+            h.mpfft_sdot_check_params.restype = ctypes.c_int
+            h.mpfft_sdot_workspace_bytes.argtypes = [_L, _L, _L, _UL, _UL]
+            h.mpfft_sdot_workspace_bytes.restype = _sz
+            h.mpfft_sdot_workspace_layout.argtypes = [_L, _L, _L, _UL, _UL, ctypes.POINTER(_sz)]
+            h.mpfft_sdot_workspace_layout.restype = ctypes.c_int
+            h.mpfft_sdot_device.argtypes = [_vp, _L, _U64, _pp, _pp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_sdot_device.restype = ctypes.c_int
+            h.mpfft_sdot_ex.argtypes = [_u64p, _L, _U64, _pp, _pp, _L, _L, _UL, _UL]
+            h.mpfft_sdot_ex.restype = ctypes.c_int
+            h.mpfft_sdot_auto.argtypes = [_u64p, _L, _U64, _pp, _pp, _L, _L]
+            h.mpfft_sdot_auto.restype = ctypes.c_int
+            h.mpfft_sdot_stage_kernels.argtypes = [_L, _U64, _L, _L, _UL, _UL, ctypes.c_char_p, _sz]
+            h.mpfft_sdot_stage_kernels.restype = ctypes.c_int
+            h.mpfft_sdot_stage.argtypes = [ctypes.c_int, _L, _vp, _vp, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
+            h.mpfft_sdot_stage.restype = ctypes.c_int
         _lib = h
     return _lib
 
@@ -770,6 +790,109 @@ def dot_stage_kernels(K, n1, n2, depth, w):
     rc = lib().mpfft_dot_stage_kernels(K, n1, n2, depth, w, buf, len(buf))
     if rc:
         raise MpfftError(rc, "mpfft_dot_stage_kernels")
+    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+
+
+# ---- signed sums of products (mpfft_sdot_*, include/mpfft.h): r = sum_i +-a_i b_i on the dot plan
+# (dot_choose, dot_plan_info, dot_max_limbs); the workspace is the dot's followed by the complement
+# scratch and the accumulator D of the subtracted b_i ----
+
+STAGE_SD_NEG = 10   # sdot_stage: d_a -> complement scratch, D <- d_b (| STAGE_ACC: D <- D + d_b)
+STAGE_SD_FIX = 11   # sdot_stage: d_r <- d_r + D - (D << 64 n1)
+SDOT_FIX_BLOCK = 4096   # limbs per block of the correction's carry chain (MPFFT_SDOT_FIX_BLOCK)
+
+
+def _neg_mask(neg):
+    """the sign mask as an int: an int is taken as it is, a sequence of booleans gives bit i = neg[i]"""
+    if isinstance(neg, (int, np.integer)) and not isinstance(neg, (bool, np.bool_)):
+        neg = int(neg)
+    else:
+        neg = sum(1 << i for i, x in enumerate(neg) if x)
+    if neg < 0 or neg >> 64:
+        raise ValueError("neg is a 64-bit mask")
+    return neg
+
+
+def sdot_to_int(limbs):
+    """the signed Python integer of a two's-complement little-endian limb array"""
+    limbs = np.ascontiguousarray(limbs, dtype=np.uint64)
+    v = int.from_bytes(limbs.tobytes(), "little")
+    return v - (1 << (64 * len(limbs))) if len(limbs) and int(limbs[-1]) >> 63 else v
+
+
+def sdot_check_params(K, neg, n1, n2, depth, w):
+    return lib().mpfft_sdot_check_params(K, _neg_mask(neg), n1, n2, depth, w)
+
+
+def sdot_workspace_bytes(K, n1, n2, depth, w):
+    return int(lib().mpfft_sdot_workspace_bytes(K, n1, n2, depth, w))
+
+
+def alloc_workspace_sdot(K, n1, n2, depth, w, device="cuda"):
+    import torch
+    nb = sdot_workspace_bytes(K, n1, n2, depth, w)
+    if nb == 0:
+        raise MpfftError(dot_check_params(K, n1, n2, depth, w), "sdot workspace")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def sdot_workspace_layout(K, n1, n2, depth, w):
+    """dot_workspace_layout's entries, then "scratch" (the complement, n1 limbs) and "D" (n2 limbs)"""
+    out = (ctypes.c_size_t * 13)()
+    rc = lib().mpfft_sdot_workspace_layout(K, n1, n2, depth, w, out)
+    if rc:
+        raise MpfftError(rc, "sdot_workspace_layout")
+    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw", "digC", "topC", "cbC", "scratch", "D")
+    return dict(zip(keys, list(out)))
+
+
+def sdot_device(d_r, d_as, d_bs, neg, n1, n2, depth, w, ws, stream=None):
+    """d_r[:n1 + n2 + 1] = sum_i +-d_as[i][:n1] * d_bs[i][:n2] in two's complement, term i subtracted
+    where neg (an int mask or a sequence of booleans) says so; as dot_device otherwise."""
+    if len(d_as) != len(d_bs):
+        raise ValueError("as many a_i as b_i")
+    rc = lib().mpfft_sdot_device(_ptr(d_r), len(d_as), _neg_mask(neg), _ptr_array(d_as), _ptr_array(d_bs), n1, n2, depth, w,
+                                 _ptr(ws), ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_sdot_device")
+
+
+def sdot(a_list, b_list, neg, depth, w):
+    """sum_i +-a_list[i] * b_list[i] as a new uint64 array of n1 + n2 + 1 limbs, two's complement
+    (host pointers, mpfft_sdot_ex); sdot_to_int gives its signed value"""
+    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
+    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
+    rc = lib().mpfft_sdot_ex(_p(r), len(a_list), _neg_mask(neg), pa, pb, n1, n2, depth, w)
+    if rc:
+        raise MpfftError(rc, f"sdot(K={len(a_list)}, n1={n1}, n2={n2}, depth={depth}, w={w})")
+    return r
+
+
+def sdot_auto(a_list, b_list, neg):
+    """sdot() with (depth, w) from dot_choose()"""
+    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
+    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
+    rc = lib().mpfft_sdot_auto(_p(r), len(a_list), _neg_mask(neg), pa, pb, n1, n2)
+    if rc:
+        raise MpfftError(rc, f"sdot_auto(K={len(a_list)}, n1={n1}, n2={n2})")
+    return r
+
+
+def sdot_stage(which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream=None):
+    """one stage on the signed sum's workspace (tests): STAGE_SD_NEG, STAGE_SD_FIX, or a dot_stage stage"""
+    rc = lib().mpfft_sdot_stage(which, K, _ptr(d_a), _ptr(d_b), _ptr(d_r), n1, n2, depth, w, _ptr(ws),
+                                ws.numel() * ws.element_size(), _stream(stream))
+    if rc:
+        raise MpfftError(rc, f"mpfft_sdot_stage({which})")
+
+
+def sdot_stage_kernels(K, neg, n1, n2, depth, w):
+    """dot_stage_kernels' dict; with a negative term fwd_columns starts with the pre-pass kernel and
+    combine ends with the correction's"""
+    buf = ctypes.create_string_buffer(768)
+    rc = lib().mpfft_sdot_stage_kernels(K, _neg_mask(neg), n1, n2, depth, w, buf, len(buf))
+    if rc:
+        raise MpfftError(rc, "mpfft_sdot_stage_kernels")
     return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
 
 

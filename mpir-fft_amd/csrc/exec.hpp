@@ -768,6 +768,39 @@ struct Exec {
         return MPFFT_OK;
     }
 
+    // ---- signed sums of products (sdot.hpp) on the regions behind the dot workspace (sd_layout) ----
+    static SdArgs sd_args(const Plan &P, unsigned char *ws)
+    {
+        const SdLayout L = sd_layout(P);
+        SdArgs d;
+        memset(&d, 0, sizeof(d));
+        d.Dl = (u64 *)(ws + L.off_d);
+        d.Dc = ws + L.off_dc;
+        d.st = (u32 *)(ws + L.off_st);
+        d.edge = (int *)(ws + L.off_edge);
+        d.n1 = P.n1;
+        d.n2 = P.n2;
+        d.total = P.total;
+        d.nb = L.nb;
+        return d;
+    }
+    static u64 *sd_scratch(const Plan &P, unsigned char *ws) { return (u64 *)(ws + sd_layout(P).off_scr); }
+
+    // a negative term's pre-pass: ~a into the scratch, D <- b (init) or D <- D + b
+    int sd_neg(const u64 *a, const u64 *b, unsigned char *ws, bool init)
+    {
+        const long n = P.n1 > P.n2 ? P.n1 : P.n2;
+        return launch(k_sdneg, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, a, b, sd_scratch(P, ws), sd_args(P, ws), init ? 1 : 0);
+    }
+
+    // r <- r + D - (D << 64 n1) over P.total limbs: the block edges and the cleared flags, then the chain
+    int sd_fix(u64 *r, unsigned char *ws)
+    {
+        const SdArgs d = sd_args(P, ws);
+        if (int rc = launch(k_sdedge, dim3((unsigned)((d.nb + 256) / 256)), dim3(256), 0, d, (const u64 *)r)) return rc;
+        return launch(k_sdfix, dim3((unsigned)d.nb), dim3(SDFIX_NT), 0, d, r);
+    }
+
     // stage 4: row DIT inverse, MFA un-twiddle at the end
     int inv_rows()
     {

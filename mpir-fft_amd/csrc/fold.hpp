@@ -497,6 +497,100 @@ __device__ __forceinline__ void fold_thread8(const FoldArgs &a, long mW, long mA
     }
 }
 
+// One block of a signed carry chain, shared by k_combine_red and k_sdfix (sdot.hpp): blocks of 8 NT
+// limbs, thread t holding limbs base + 8 t .. + 7 as 128-bit signed sums (lo, hi) -- hi small -- and
+// H[t] the hi of the limb below its first (H[0]: of the limb below the block, H written and a
+// barrier passed before the call).  Per limb the transfer function of its value with the overflow
+// from below, composed over the thread, the wave (cf_wave_scan), the workgroup (WF) and the blocks
+// below by decoupled look-back over ticket-ordered blocks (b: this block's ticket; st as
+// k_combine_red describes it); the resolved limbs go through Lx to r[base ..), coalesced.  The
+// caller's barrier behind the call closes the reads of Lx.
+template <int NT>
+__device__ __forceinline__ void cf_chain_block(const u64 (&lo)[8], const int (&hi)[8], const int *H, u32 *WF, int &sh_cin,
+                                               u64 *Lx, u32 *st, long b, long base, long total, int t, int lane, int wave,
+                                               u64 *r)
+{
+    constexpr int V = 8, NW = NT / 64;
+    u64 u[8];
+    u32 gk = 0;   // limb k's local carry + 1 at bits 2k (3: past the end, transparent)
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const bool real = base + 8L * t + k < total;
+        const int hin = k ? hi[k - 1] : H[t];
+        const u64 v = lo[k] + (u64)(i64)hin;
+        const int g = hin >= 0 ? (v < lo[k] ? 1 : 0) : (v > lo[k] ? -1 : 0);
+        u[k] = v;
+        gk |= (real ? (u32)(g + 1) : 3u) << (2 * k);
+    }
+    auto fk = [&](int k) -> u32 {
+        const u32 gq = (gk >> (2 * k)) & 3u;
+        return gq == 3u ? CF_ID : cf_make((int)gq - 1, u[k]);
+    };
+    // the thread's composite, last limb first: a limb that neither is 0 nor all ones maps every
+    // carry-in to its own carry, so the composite almost always stops at limb 7
+    u32 F = fk(7);
+#pragma unroll
+    for (int k = 6; k >= 0; --k)
+        if (!cf_const(F)) F = cf_then(fk(k), F);
+    u32 I, Ex;
+    if (__ballot(!cf_const(F)) == 0) {   // every lane constant: lane L's carry-in is lane L - 1's carry-out
+        I = F;
+        Ex = (u32)__shfl_up((int)F, 1);
+    } else {
+        I = cf_wave_scan(F, lane);
+        Ex = (u32)__shfl_up((int)I, 1);
+    }
+    if (lane == 0) Ex = CF_ID;
+    if (lane == 63) WF[wave] = I;
+    __syncthreads();
+    // the composites of the waves below (Wp) and of the block (Fb); a constant wave function
+    // overrides everything before it, the common case
+    u32 Wp = CF_ID, Fb = CF_ID;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const u32 f = WF[w];
+        const u32 nb = cf_const(f) ? f : cf_then(Fb, f);
+        if (w < wave) Wp = nb;
+        Fb = nb;
+    }
+    if (t == 0) {
+        int cin = 0;
+        if (b == 0) {
+            __hip_atomic_store(&st[0], 9u + (u32)cf_apply(Fb, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        } else {
+            const bool cst = cf_const(Fb);
+            __hip_atomic_store(&st[b], cst ? 9u + (u32)cf_apply(Fb, 0) : 16u + Fb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            u32 acc = CF_ID;
+            for (long q = b - 1;; --q) {
+                u32 f;
+                while ((f = __hip_atomic_load(&st[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u)
+                    __builtin_amdgcn_s_sleep(1);
+                if (f < 16u) {
+                    cin = cf_apply(acc, (int)f - 9);
+                    break;
+                }
+                acc = cf_then(f - 16u, acc);
+            }
+            if (!cst) __hip_atomic_store(&st[b], 9u + (u32)cf_apply(Fb, cin), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        sh_cin = cin;
+    }
+    __syncthreads();
+    int c = cf_apply(cf_then(Wp, Ex), sh_cin);
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        Lx[t * V + k] = u[k] + (u64)(i64)c;
+        const int gq = (int)((gk >> (2 * k)) & 3u) - 1;   // 2: past the end (transparent)
+        c = gq == 2 ? c : gq + (c == 1 && u[k] == MPF_MAXL) - (c == -1 && u[k] == 0);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < V; ++k) {
+        const long m = base + k * NT + t;
+        if (m < total) r[m] = Lx[k * NT + t];
+    }
+}
+
 // k_combine_red<KM, NT>: the product from the reduced-form coefficients, blocks of 8 NT limbs
 // (8 consecutive limbs per thread), one launch: window sums, a signed carry chain per block as
 // transfer functions (wave scan + workgroup scan), and the decoupled look-back of k_combine1 over
@@ -546,84 +640,7 @@ __global__ __launch_bounds__(NT, KM <= 3 ? 2048 / NT : 1) void k_combine_red(Fol
             H[0] = h0;
         }
         __syncthreads();
-        u64 u[8];
-        u32 gk = 0;   // limb k's local carry + 1 at bits 2k (3: past the end, transparent)
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const bool real = base + 8L * t + k < total;
-            const int hin = k ? hi[k - 1] : H[t];
-            const u64 v = lo[k] + (u64)(i64)hin;
-            const int g = hin >= 0 ? (v < lo[k] ? 1 : 0) : (v > lo[k] ? -1 : 0);
-            u[k] = v;
-            gk |= (real ? (u32)(g + 1) : 3u) << (2 * k);
-        }
-        auto fk = [&](int k) -> u32 {
-            const u32 gq = (gk >> (2 * k)) & 3u;
-            return gq == 3u ? CF_ID : cf_make((int)gq - 1, u[k]);
-        };
-        // the thread's composite, last limb first: a limb that neither is 0 nor all ones maps every
-        // carry-in to its own carry, so the composite almost always stops at limb 7
-        u32 F = fk(7);
-#pragma unroll
-        for (int k = 6; k >= 0; --k)
-            if (!cf_const(F)) F = cf_then(fk(k), F);
-        u32 I, Ex;
-        if (__ballot(!cf_const(F)) == 0) {   // every lane constant: lane L's carry-in is lane L - 1's carry-out
-            I = F;
-            Ex = (u32)__shfl_up((int)F, 1);
-        } else {
-            I = cf_wave_scan(F, lane);
-            Ex = (u32)__shfl_up((int)I, 1);
-        }
-        if (lane == 0) Ex = CF_ID;
-        if (lane == 63) WF[wave] = I;
-        __syncthreads();
-        // the composites of the waves below (Wp) and of the block (Fb); a constant wave function
-        // overrides everything before it, the common case
-        u32 Wp = CF_ID, Fb = CF_ID;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const u32 f = WF[w];
-            const u32 nb = cf_const(f) ? f : cf_then(Fb, f);
-            if (w < wave) Wp = nb;
-            Fb = nb;
-        }
-        if (t == 0) {
-            int cin = 0;
-            if (b == 0) {
-                __hip_atomic_store(&st[0], 9u + (u32)cf_apply(Fb, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                const bool cst = cf_const(Fb);
-                __hip_atomic_store(&st[b], cst ? 9u + (u32)cf_apply(Fb, 0) : 16u + Fb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                u32 acc = CF_ID;
-                for (long q = b - 1;; --q) {
-                    u32 f;
-                    while ((f = __hip_atomic_load(&st[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u)
-                        __builtin_amdgcn_s_sleep(1);
-                    if (f < 16u) {
-                        cin = cf_apply(acc, (int)f - 9);
-                        break;
-                    }
-                    acc = cf_then(f - 16u, acc);
-                }
-                if (!cst) __hip_atomic_store(&st[b], 9u + (u32)cf_apply(Fb, cin), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            sh_cin = cin;
-        }
-        __syncthreads();
-        int c = cf_apply(cf_then(Wp, Ex), sh_cin);
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            Lx[t * V + k] = u[k] + (u64)(i64)c;
-            const int gq = (int)((gk >> (2 * k)) & 3u) - 1;   // 2: past the end (transparent)
-            c = gq == 2 ? c : gq + (c == 1 && u[k] == MPF_MAXL) - (c == -1 && u[k] == 0);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < V; ++k) {
-            const long m = base + k * NT + t;
-            if (m < total) r[m] = Lx[k * NT + t];
-        }
+        cf_chain_block<NT>(lo, hi, H, WF, sh_cin, Lx, st, b, base, total, t, lane, wave, r);
         __syncthreads();   // every read of this ticket's LDS done
         if (t == 0) sh_b = nxt;
         __syncthreads();

@@ -34,6 +34,7 @@
 #include "dot.hpp"
 #include "combine.hpp"
 #include "fold.hpp"
+#include "sdot.hpp"
 #include "nega.hpp"
 #include "negaw.hpp"
 #include "cyc.hpp"
@@ -309,9 +310,16 @@ static int run_all_mod(const Plan &P, u64 *d_r, const u64 *d_a, const u64 *d_b, 
 // Profiling: every term claims a call slot and marks its forward columns, rows and pointwise; the
 // last term's slot carries the inverse side, the others mark those boundaries at once (empty
 // stages) -- mpfft_profile_end's sums are the sum's stage times, its call count the terms.
+// neg (mpfft_sdot_*, sdot.hpp): bit i set, term i is subtracted.  Its pre-pass (k_sdneg: ~a_i into the
+// scratch behind the dot workspace, D <- D + b_i, the first one initialising D) is queued in front of
+// its forward columns, which read the scratch in place of a_i, and counts with that stage; behind the
+// combine, and counted with it, the correction d_r <- d_r + D - (D << 64 n1) (k_sdedge, k_sdfix).
+// ws then has sd_layout's regions; neg == 0 launches neither and touches none of them.
 template <typename Term>
-static int run_dot(const Plan &P, long K, u64 *d_r, unsigned char *ws, hipStream_t s, Term term)
+static int run_dot(const Plan &P, long K, u64 *d_r, unsigned char *ws, hipStream_t s, Term term, u64 neg = 0)
 {
+    static_assert(SDFIX_CB == SD_FIX_BLOCK && SD_FIX_BLOCK == MPFFT_SDOT_FIX_BLOCK, "one chain block size");
+    bool d_init = true;
     Exec X(P, s);
     X.single(ws);
     X.zflags = X.comb_flags(ws);
@@ -326,6 +334,11 @@ static int run_dot(const Plan &P, long K, u64 *d_r, unsigned char *ws, hipStream
         ProfCall pc;
         pc.mark(0, s);
         if ((rc = term(i, &a, &b))) return rc;
+        if ((neg >> i) & 1) {
+            if ((rc = X.sd_neg(a, b, ws, d_init))) return rc;
+            d_init = false;
+            a = Exec::sd_scratch(P, ws);
+        }
         X.col = X.row = ab;
         if (i == 0 && in_place) X.view_op0(X.cview);
         if ((rc = X.fwd_columns(a, P.n1, b, P.n2, 2))) return rc;
@@ -346,6 +359,7 @@ static int run_dot(const Plan &P, long K, u64 *d_r, unsigned char *ws, hipStream
         if ((rc = X.scale())) return rc;
         pc.mark(6, s);
         rc = X.fold ? X.combine_fold(d_r, ws, X.dbl_lo, X.dbl_hi) : X.combine_single(d_r, ws);
+        if (!rc && neg) rc = X.sd_fix(d_r, ws);
         pc.mark(7, s);
     }
     return rc;
@@ -1785,8 +1799,10 @@ int mpfft_dot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b,
 
 // Host operands: the context's io buffer holds one term's operands and, behind them, the sum; each
 // term's copies are queued on the context's stream in front of its forward passes.
-int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
-                 unsigned long depth, unsigned long w)
+// neg: mpfft_sdot_ex's sign mask (the workspace then has sd_layout's regions behind the dot's; D lives
+// there, so no operand is kept after its term)
+static int dot_host(uint64_t *r, long K, u64 neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
+                    unsigned long depth, unsigned long w)
 {
     Plan P;
     int rc = make_plan_dot(&P, K, n1, n2, depth, w);
@@ -1797,7 +1813,7 @@ int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *
     if ((rc = host_ctx(&C, &dev))) return rc;
     std::lock_guard<std::mutex> lk(C->mu);
     if (!C->stream) HIPCHK(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking));
-    if ((rc = ensure_buf((void **)&C->ws, &C->ws_bytes, P.bytes))) return rc;
+    if ((rc = ensure_buf((void **)&C->ws, &C->ws_bytes, neg ? sd_layout(P).bytes : P.bytes))) return rc;
     if ((rc = ensure_buf((void **)&C->io, &C->io_bytes, (size_t)(n1 + n2 + P.total) * 8))) return rc;
     u64 *d_a = C->io, *d_b = d_a + n1, *d_r = d_b + n2;
     hipStream_t s = C->stream;
@@ -1808,7 +1824,7 @@ int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *
         *pa = d_a;
         *pb = d_b;
         return (int)MPFFT_OK;
-    });
+    }, neg);
     if (rc) {
         (void)hipStreamSynchronize(s);
         return rc;
@@ -1818,12 +1834,120 @@ int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *
     return MPFFT_OK;
 }
 
+int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
+                 unsigned long depth, unsigned long w)
+{
+    return dot_host(r, K, 0, a, b, n1, n2, depth, w);
+}
+
 int mpfft_dot_auto(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2)
 {
     unsigned long d = 0, wv = 0;
     const int rc = mpfft_dot_choose(K, n1, n2, &d, &wv);
     if (rc) return rc;
     return mpfft_dot_ex(r, K, a, b, n1, n2, d, wv);
+}
+
+// ---- signed sums of products (mpfft_sdot_*, MPFFT_VERSION 9; sdot.hpp) -------------------------
+// the dot plan; MPFFT_EINVAL for a mask bit at or above K
+static int make_plan_sdot(Plan *p, long K, u64 neg, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    const int rc = make_plan_dot(p, K, n1, n2, depth, w);
+    if (rc) return rc;
+    return K < 64 && (neg >> K) ? MPFFT_EINVAL : MPFFT_OK;
+}
+
+int mpfft_sdot_check_params(long K, uint64_t neg, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_sdot(&P, K, neg, n1, n2, depth, w);
+}
+
+size_t mpfft_sdot_workspace_bytes(long K, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan_dot(&P, K, n1, n2, depth, w)) return 0;
+    return sd_layout(P).bytes;
+}
+
+int mpfft_sdot_workspace_layout(long K, long n1, long n2, unsigned long depth, unsigned long w, size_t *out)
+{
+    Plan P;
+    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    if ((rc = mpfft_dot_workspace_layout(K, n1, n2, depth, w, out))) return rc;
+    const SdLayout L = sd_layout(P);
+    out[11] = L.off_scr;
+    out[12] = L.off_d;
+    return MPFFT_OK;
+}
+
+int mpfft_sdot_device(uint64_t *d_r, long K, uint64_t neg, const uint64_t *const *d_a, const uint64_t *const *d_b, long n1,
+                      long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_sdot(&P, K, neg, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!d_r || !d_a || !d_b) return MPFFT_EINVAL;
+    if (!d_ws || ws_bytes < sd_layout(P).bytes) return MPFFT_ENOMEM;
+    (void)hipGetLastError();
+    return run_dot(P, K, d_r, (unsigned char *)d_ws, (hipStream_t)stream, [&](long i, const u64 **a, const u64 **b) {
+        *a = d_a[i];
+        *b = d_b[i];
+        return *a && *b ? MPFFT_OK : MPFFT_EINVAL;
+    }, neg);
+}
+
+int mpfft_sdot_ex(uint64_t *r, long K, uint64_t neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
+                  unsigned long depth, unsigned long w)
+{
+    Plan P;
+    const int rc = make_plan_sdot(&P, K, neg, n1, n2, depth, w);
+    if (rc) return rc;
+    return dot_host(r, K, neg, a, b, n1, n2, depth, w);
+}
+
+int mpfft_sdot_auto(uint64_t *r, long K, uint64_t neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2)
+{
+    unsigned long d = 0, wv = 0;
+    if (K >= 1 && K < 64 && (neg >> K)) return MPFFT_EINVAL;
+    const int rc = mpfft_dot_choose(K, n1, n2, &d, &wv);
+    if (rc) return rc;
+    return mpfft_sdot_ex(r, K, neg, a, b, n1, n2, d, wv);
+}
+
+// The dot's seven fields; with a negative term the pre-pass in front of the forward columns' and the
+// correction behind the combine's
+int mpfft_sdot_stage_kernels(long K, uint64_t neg, long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
+{
+    Plan P;
+    int rc = make_plan_sdot(&P, K, neg, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!buf || !len) return MPFFT_EINVAL;
+    std::vector<char> tmp(len);
+    if ((rc = mpfft_dot_stage_kernels(K, n1, n2, depth, w, tmp.data(), len))) return rc;
+    std::string names = tmp.data();
+    if (neg) names = "k_sdneg + " + names + " + k_sdedge + k_sdfix (blocks of 4096 limbs)";
+    return copy_out(names, buf, len);
+}
+
+int mpfft_sdot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1, long n2,
+                     unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    const int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    if (rc) return rc;
+    const int st = stage & ~MPFFT_STAGE_ACC;
+    const bool acc = (stage & MPFFT_STAGE_ACC) != 0;
+    if (acc && st != MPFFT_STAGE_SD_NEG && st != MPFFT_STAGE_POINTWISE) return MPFFT_EINVAL;
+    if (!d_ws || ws_bytes < sd_layout(P).bytes) return MPFFT_ENOMEM;
+    if (st != MPFFT_STAGE_SD_NEG && st != MPFFT_STAGE_SD_FIX)   // the dot workspace at the front of this one
+        return mpfft_dot_stage(stage, K, d_a, d_b, d_r, n1, n2, depth, w, d_ws, ws_bytes, stream);
+    (void)hipGetLastError();
+    Exec X(P, (hipStream_t)stream);
+    X.single((unsigned char *)d_ws);
+    if (st == MPFFT_STAGE_SD_NEG) return d_a && d_b ? X.sd_neg(d_a, d_b, (unsigned char *)d_ws, !acc) : MPFFT_EINVAL;
+    return d_r ? X.sd_fix(d_r, (unsigned char *)d_ws) : MPFFT_EINVAL;
 }
 
 // release the calling device's cached workspace (the next call re-allocates)

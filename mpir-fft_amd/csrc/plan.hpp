@@ -394,6 +394,29 @@ static int make_plan_dot(Plan *p, long K, long n1, long n2, unsigned long depth,
     return MPFFT_OK;
 }
 
+// Signed sum of products (mpfft_sdot_*, sdot.hpp): the dot plan and its workspace, and behind it --
+// whatever the sign mask -- the complement scratch (n1 limbs), D in carry-save form (n2 limbs, n2
+// overflow bytes), and k_sdfix's flags, ticket counter and block-edge overflows.  A dot workspace
+// laid at the front is valid as it stands.
+struct SdLayout {
+    size_t off_scr, off_d, off_dc, off_st, off_edge, bytes;
+    long nb;   // k_sdfix's chain blocks
+};
+static const long SD_FIX_BLOCK = 4096;   // limbs per k_sdfix block (SDFIX_CB, MPFFT_SDOT_FIX_BLOCK)
+static SdLayout sd_layout(const Plan &P)
+{
+    SdLayout L;
+    L.nb = (P.total + SD_FIX_BLOCK - 1) / SD_FIX_BLOCK;
+    size_t o = align_up(P.bytes, 256);
+    L.off_scr = o; o += align_up((size_t)P.n1 * 8, 256);
+    L.off_d = o; o += align_up((size_t)P.n2 * 8, 256);
+    L.off_dc = o; o += align_up((size_t)P.n2, 256);
+    L.off_st = o; o += align_up((size_t)(L.nb + 1) * 4, 256);
+    L.off_edge = o; o += align_up((size_t)L.nb * 4, 256);
+    L.bytes = o;
+    return L;
+}
+
 // Squaring plan: the multiply's plan for n by n limbs -- the same split, trunc, fold, ltw and
 // fuse_rows -- with operand B's arrays taken out of the layout.
 static int make_plan_sqr(Plan *p, long n, unsigned long depth, unsigned long w)
