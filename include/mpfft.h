@@ -67,7 +67,16 @@ int mpfft_release(void);
 
 /* Device-resident multiply: all pointers are device memory, work is queued on
  * `stream` (a hipStream_t, NULL = default) and not synchronised.  d_ws must hold
- * mpfft_workspace_bytes(n1, n2, depth, w) bytes. */
+ * mpfft_workspace_bytes(n1, n2, depth, w) bytes.
+ * Alignment, for this entry and for the mpfft_sqr_, mpfft_mulmod_, mpfft_mulmodw_, mpfft_mulmodm1_,
+ * mpfft_precomp_ / mpfft_mul_precomp_, mpfft_dot_ and mpfft_sdot_ device and stage entries below:
+ * operands and results (d_r, d_i1, d_i2, d_a, d_b and the pointers in a term array) need limb
+ * (8-byte) alignment only, so rp + k is a valid argument as it is for the mpn_* calls these
+ * replace (tests/test_gpu_limb_aligned.py).  mpfft_mul6_device, the mpfft_shard_* entries and
+ * mpfft_mul_multi_device read their operands limb by limb as well, but no test runs them on such
+ * pointers: give those 16-byte aligned ones.  A workspace d_ws and a cache d_pre must be 256-byte
+ * aligned (their arrays sit at 256-byte offsets; hipMalloc returns such pointers); the entries do
+ * not check this and return no status for a misaligned one. */
 int mpfft_mul_device(uint64_t *d_r, const uint64_t *d_i1, long n1, const uint64_t *d_i2, long n2,
                      unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
 

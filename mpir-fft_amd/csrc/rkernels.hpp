@@ -782,10 +782,12 @@ __global__ __launch_bounds__(rp_nt(1024 * PP, LOGG, DIR), 4) void k_rpass(PassAr
         // staged form (whole operands): every live slot's source span -- bits1 < N/2 bits, so at most
         // l/2 + 2 limbs from the even limb below its first -- read with coalesced 16-B loads by
         // consecutive threads, all slots' loads in flight at once, parked in the exchange slots; each
-        // thread then reads its three limbs per pair back from LDS
+        // thread then reads its three limbs per pair back from LDS.  The 16-B loads start at an even
+        // limb index, so they are aligned only when the operand is: an operand that is only
+        // limb-aligned (mpfft.h: rp + k) takes the guarded 8-B loads below (workgroup-uniform)
         constexpr int SWP = l / 4 + 2, SW = 2 * SWP, KR = (G * SWP + NT - 1) / NT;
         constexpr bool STAGE = (size_t)G * SW * 8 <= (size_t)NX * RX<PP>::SB;
-        if (STAGE && !a.src_chunk) {
+        if (STAGE && !a.src_chunk && !((size_t)src & 15)) {
             u64 *S = (u64 *)smem;
             const long nsv = a.nsrc[op];
             auto slot_q0 = [&](int i) -> long {   // the even source limb staged slot i starts at
