@@ -65,6 +65,90 @@ class MpfftError(RuntimeError):
         self.code = code
 
 
+_I, _SZ, _U64, _cp = ctypes.c_int, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_char_p
+_ip, _lp, _ulp, _szp, _pp = (ctypes.POINTER(t) for t in (_I, _L, _UL, _SZ, _vp))
+_MUL = [_L, _L, _UL, _UL]    # (n1, n2, depth, w)
+_MOD = [_L, _UL, _UL]        # (L, depth, w), and a square's (n, depth, w)
+_DOT = [_L] + _MUL           # (K, n1, n2, depth, w)
+_WS = [_vp, _SZ, _vp]        # (d_ws, ws_bytes, stream)
+_TEXT = [_cp, _SZ]           # (buf, len)
+
+
+def _mod_signatures(fam, sq):
+    """the entries every family of products modulo 2^B +- 1 has: mpfft_<fam>_* and the squares' mpfft_<sq>_*"""
+    return [("mpfft_%s_check_params" % fam, _I, _MOD), ("mpfft_%s_ex" % fam, _I, [_u64p, _u64p, _u64p] + _MOD),
+            ("mpfft_%s_ex" % sq, _I, [_u64p, _u64p] + _MOD), ("mpfft_%s_device" % fam, _I, [_vp, _vp, _vp] + _MOD + _WS),
+            ("mpfft_%s_device" % sq, _I, [_vp, _vp] + _MOD + _WS), ("mpfft_%s_workspace_bytes" % fam, _SZ, _MOD + [_I]),
+            ("mpfft_%s_plan_info" % fam, _I, _MOD + [_lp]), ("mpfft_%s_workspace_layout" % fam, _I, _MOD + [_I, _szp]),
+            ("mpfft_%s_stage" % fam, _I, [_I, _vp, _vp, _vp] + _MOD + [_I] + _WS),
+            ("mpfft_%s_stage_kernels" % fam, _I, _MOD + [_I] + _TEXT), ("mpfft_%s_choose" % fam, _I, [_L, _ulp, _ulp]),
+            ("mpfft_%s_next_size" % fam, _I, [_L, _lp, _ulp, _ulp])]
+
+
+def _signatures():
+    """(name, restype, argtypes) of every function of include/mpfft.h that is called from here: a wrong entry
+    corrupts arguments silently, so tests/test_signature_table.py holds each against the header's prototype"""
+    return [
+        ("new_mpn_mul", None, [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]),
+        ("mpfft_mul_ex", _I, [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]),
+        ("mpfft_profile_begin", _I, [_I]), ("mpfft_profile_end", _I, [ctypes.POINTER(ctypes.c_float), _ip]),
+        ("mpfft_stage_kernels", _I, _MUL + _TEXT), ("mpfft_inv_columns_schedule", _I, _MUL + _TEXT),
+        ("mpfft_release", _I, []),
+        ("mpfft_mul_device", _I, [_vp, _vp, _L, _vp, _L, _UL, _UL] + _WS),
+        ("mpfft_stage", _I, [_I, _vp, _vp, _vp] + _MUL + _WS),
+        ("mpfft_workspace_bytes", _SZ, _MUL), ("mpfft_check_params", _I, _MUL), ("mpfft_plan_info", _I, _MUL + [_lp]),
+        ("mpfft_workspace_layout", _I, _MUL + [_szp]),
+        ("mpfft_strerror", _cp, [_I]), ("mpfft_version", _I, []), ("mpfft_fill_random", None, [_u64p, _L, _U64]),
+        ("mpfft_shard_stage", _I, [_I, ctypes.POINTER(_Shard), _vp, _vp, _vp]),
+        ("mpfft_shard_stage_rows", _I, [_I, ctypes.POINTER(_Shard), _I, _I, _vp]),
+        ("mpfft_shard_row_fused", _I, _MUL + [_I]), ("mpfft_shard_combine_tmp_bytes", _SZ, _MUL + [_I]),
+        ("mpfft_shard_combine", _I, [ctypes.POINTER(_Shard), _I, _vp, _vp, _vp, _vp, _vp, _SZ, _vp]),
+        ("mpfft_shard_partition", _I, _MUL + [_I, _lp, _lp]), ("mpfft_shard_stripes", _L, _MUL + [_I, _lp, _L]),
+        ("mpfft_shard_exchange_plan", _L, _MUL + [_I, _I, ctypes.POINTER(_Copy), _L]),
+        ("mpfft_shard_halo_plan", _L, _MUL + [_I, ctypes.POINTER(_Copy), _L]),
+        ("mpfft_shard_src_limbs", _L, _MUL + [_I]), ("mpfft_shard_pack", _I, _MUL + [_I, _I, _u64p, _L, _u64p]),
+        ("mpfft_mul_multi_device", _I, _MUL + [_I, _ip, _pp, _pp, _pp, _pp]),
+        ("mpfft_mul_multi", _I, [_u64p, _u64p, _L, _u64p, _L, _UL, _UL, _I, _ip]),
+        ("mpfft_multi_release", _I, []), ("mpfft_multi_schedule", _L, _MUL + [_I, _I] + _TEXT),
+        ("mpfft_set_devices", _I, [_I, _ip, _L]), ("mpfft_last_ngpus", _I, []),
+        ("mpfft_choose", _I, [_L, _L, _ulp, _ulp]), ("mpfft_mul_auto", _I, [_u64p, _u64p, _L, _u64p, _L]),
+        ("new_mpn_mul6", None, [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]),
+        ("mpfft_mul6_ex", _I, [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]),
+        ("mpfft_mul6_device", _I, [_vp, _vp, _L, _vp, _L, _UL, _UL] + _WS),
+        ("mpfft_workspace_bytes6", _SZ, _MUL), ("mpfft_check_params6", _I, _MUL), ("mpfft_plan_info6", _I, _MUL + [_lp]),
+        # MPFFT_VERSION 3: squares
+        ("mpfft_sqr_ex", _I, [_u64p, _u64p] + _MOD), ("mpfft_sqr_auto", _I, [_u64p, _u64p, _L]),
+        ("mpfft_sqr_device", _I, [_vp, _vp] + _MOD + _WS), ("mpfft_sqr_workspace_bytes", _SZ, _MOD),
+        ("mpfft_sqr_workspace_layout", _I, _MOD + [_szp]), ("mpfft_sqr_stage", _I, [_I, _vp, _vp] + _MOD + _WS),
+        ("mpfft_sqr_stage_kernels", _I, _MOD + _TEXT),
+        # 5: the cached operand
+        ("mpfft_precomp_bytes", _SZ, _MUL), ("mpfft_precomp_device", _I, [_vp, _SZ, _vp] + _MUL + _WS),
+        ("mpfft_mul_precomp_workspace_bytes", _SZ, _MUL),
+        ("mpfft_mul_precomp_device", _I, [_vp, _vp, _L, _vp, _SZ, _L, _UL, _UL] + _WS),
+        ("mpfft_precomp_stage_kernels", _I, _MUL + _TEXT), ("mpfft_precomp_stage", _I, [_I, _vp, _SZ, _vp] + _MUL + _WS),
+        ("mpfft_mul_precomp_stage", _I, [_I, _vp, _vp, _SZ, _vp] + _MUL + _WS),
+        ("mpfft_precomp_create", _I, [_pp, _u64p, _L, _L, _UL, _UL]), ("mpfft_mul_precomp_ex", _I, [_u64p, _u64p, _L, _vp]),
+        ("mpfft_precomp_destroy", None, [_vp]),
+        # 6: mod 2^B - 1 and its cached operand
+        ("mpfft_mulmodm1_precomp_bytes", _SZ, _MOD), ("mpfft_mulmodm1_precomp_device", _I, [_vp, _SZ, _vp] + _MOD + _WS),
+        ("mpfft_mulmodm1_mul_precomp_device", _I, [_vp, _vp, _vp, _SZ] + _MOD + _WS),
+        # 8: sums of products
+        ("mpfft_dot_check_params", _I, _DOT), ("mpfft_dot_plan_info", _I, _DOT + [_lp]),
+        ("mpfft_dot_choose", _I, [_L, _L, _L, _ulp, _ulp]), ("mpfft_dot_workspace_bytes", _SZ, _DOT),
+        ("mpfft_dot_workspace_layout", _I, _DOT + [_szp]), ("mpfft_dot_device", _I, [_vp, _L, _pp, _pp] + _MUL + _WS),
+        ("mpfft_dot_ex", _I, [_u64p, _L, _pp, _pp] + _MUL), ("mpfft_dot_auto", _I, [_u64p, _L, _pp, _pp, _L, _L]),
+        ("mpfft_dot_stage_kernels", _I, _DOT + _TEXT), ("mpfft_dot_stage", _I, [_I, _L, _vp, _vp, _vp] + _MUL + _WS),
+        # 9: signed sums
+        ("mpfft_sdot_check_params", _I, [_L, _U64] + _MUL), ("mpfft_sdot_workspace_bytes", _SZ, _DOT),
+        ("mpfft_sdot_workspace_layout", _I, _DOT + [_szp]),
+        ("mpfft_sdot_device", _I, [_vp, _L, _U64, _pp, _pp] + _MUL + _WS),
+        ("mpfft_sdot_ex", _I, [_u64p, _L, _U64, _pp, _pp] + _MUL), ("mpfft_sdot_auto", _I, [_u64p, _L, _U64, _pp, _pp, _L, _L]),
+        ("mpfft_sdot_stage_kernels", _I, [_L, _U64] + _MUL + _TEXT),
+        ("mpfft_sdot_stage", _I, [_I, _L, _vp, _vp, _vp] + _MUL + _WS),
+        # 4, 7, 6: mod 2^B + 1, with the low-word CRT, mod 2^B - 1
+    ] + _mod_signatures("mulmod", "sqrmod") + _mod_signatures("mulmodw", "sqrmodw") + _mod_signatures("mulmodm1", "sqrmodm1")
+
+
 def lib():
     """The loaded libmpfft.so (raises if it was not built -- no fallback)."""
     global _lib
@@ -81,262 +165,11 @@ def lib():
         except ImportError:
             pass
         h = ctypes.CDLL(LIB_PATH)
-        h.new_mpn_mul.argtypes = [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]
-        h.new_mpn_mul.restype = None
-        h.mpfft_mul_ex.argtypes = [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]
-        h.mpfft_mul_ex.restype = ctypes.c_int
-        h.mpfft_profile_begin.argtypes = [ctypes.c_int]
-        h.mpfft_profile_begin.restype = ctypes.c_int
-        h.mpfft_profile_end.argtypes = [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)]
-        h.mpfft_profile_end.restype = ctypes.c_int
-        h.mpfft_stage_kernels.argtypes = [_L, _L, _UL, _UL, ctypes.c_char_p, ctypes.c_size_t]
-        h.mpfft_stage_kernels.restype = ctypes.c_int
-        h.mpfft_release.argtypes = []
-        h.mpfft_release.restype = ctypes.c_int
-        h.mpfft_mul_device.argtypes = [_vp, _vp, _L, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-        h.mpfft_mul_device.restype = ctypes.c_int
-        h.mpfft_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-        h.mpfft_stage.restype = ctypes.c_int
-        h.mpfft_workspace_bytes.argtypes = [_L, _L, _UL, _UL]
-        h.mpfft_workspace_bytes.restype = ctypes.c_size_t
-        h.mpfft_check_params.argtypes = [_L, _L, _UL, _UL]
-        h.mpfft_check_params.restype = ctypes.c_int
-        h.mpfft_plan_info.argtypes = [_L, _L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
-        h.mpfft_plan_info.restype = ctypes.c_int
-        h.mpfft_workspace_layout.argtypes = [_L, _L, _UL, _UL, ctypes.POINTER(ctypes.c_size_t)]
-        h.mpfft_workspace_layout.restype = ctypes.c_int
-        h.mpfft_strerror.argtypes = [ctypes.c_int]
-        h.mpfft_strerror.restype = ctypes.c_char_p
-        h.mpfft_version.argtypes = []
-        h.mpfft_version.restype = ctypes.c_int
-        h.mpfft_fill_random.argtypes = [_u64p, _L, ctypes.c_uint64]
-        h.mpfft_fill_random.restype = None
-        h.mpfft_shard_stage.argtypes = [ctypes.c_int, ctypes.POINTER(_Shard), _vp, _vp, _vp]
-        h.mpfft_shard_stage.restype = ctypes.c_int
-        h.mpfft_shard_stage_rows.argtypes = [ctypes.c_int, ctypes.POINTER(_Shard), ctypes.c_int, ctypes.c_int, _vp]
-        h.mpfft_shard_stage_rows.restype = ctypes.c_int
-        h.mpfft_shard_row_fused.argtypes = [_L, _L, _UL, _UL, ctypes.c_int]
-        h.mpfft_shard_row_fused.restype = ctypes.c_int
-        h.mpfft_shard_combine_tmp_bytes.argtypes = [_L, _L, _UL, _UL, ctypes.c_int]
-        h.mpfft_shard_combine_tmp_bytes.restype = ctypes.c_size_t
-        h.mpfft_shard_combine.argtypes = [ctypes.POINTER(_Shard), ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
-                                          ctypes.c_size_t, _vp]
-        h.mpfft_shard_combine.restype = ctypes.c_int
-        _lp = ctypes.POINTER(ctypes.c_long)
-        h.mpfft_shard_partition.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, _lp, _lp]
-        h.mpfft_shard_partition.restype = ctypes.c_int
-        h.mpfft_shard_stripes.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, _lp, _L]
-        h.mpfft_shard_stripes.restype = ctypes.c_long
-        h.mpfft_shard_exchange_plan.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, ctypes.c_int,
-                                                ctypes.POINTER(_Copy), _L]
-        h.mpfft_shard_exchange_plan.restype = ctypes.c_long
-        h.mpfft_shard_halo_plan.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, ctypes.POINTER(_Copy), _L]
-        h.mpfft_shard_halo_plan.restype = ctypes.c_long
-        h.mpfft_shard_src_limbs.argtypes = [_L, _L, _UL, _UL, ctypes.c_int]
-        h.mpfft_shard_src_limbs.restype = ctypes.c_long
-        h.mpfft_shard_pack.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, ctypes.c_int, _u64p, _L, _u64p]
-        h.mpfft_shard_pack.restype = ctypes.c_int
-        h.mpfft_mul_multi_device.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
-                                             ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp),
-                                             ctypes.POINTER(_vp)]
-        h.mpfft_mul_multi_device.restype = ctypes.c_int
-        h.mpfft_mul_multi.argtypes = [_u64p, _u64p, _L, _u64p, _L, _UL, _UL, ctypes.c_int,
-                                      ctypes.POINTER(ctypes.c_int)]
-        h.mpfft_mul_multi.restype = ctypes.c_int
-        h.mpfft_multi_release.argtypes = []
-        h.mpfft_multi_release.restype = ctypes.c_int
-        if hasattr(h, "mpfft_multi_schedule"):   # (older libraries in A/B runs lack it)
-            h.mpfft_multi_schedule.argtypes = [_L, _L, _UL, _UL, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
-                                               ctypes.c_size_t]
-            h.mpfft_multi_schedule.restype = ctypes.c_long
-        h.mpfft_set_devices.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), _L]
-        h.mpfft_set_devices.restype = ctypes.c_int
-        h.mpfft_last_ngpus.argtypes = []
-        h.mpfft_last_ngpus.restype = ctypes.c_int
-        h.mpfft_choose.argtypes = [_L, _L, ctypes.POINTER(ctypes.c_ulong), ctypes.POINTER(ctypes.c_ulong)]
-        h.mpfft_choose.restype = ctypes.c_int
-        h.mpfft_mul_auto.argtypes = [_u64p, _u64p, _L, _u64p, _L]
-        h.mpfft_mul_auto.restype = ctypes.c_int
-        h.new_mpn_mul6.argtypes = [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]
-        h.new_mpn_mul6.restype = None
-        h.mpfft_mul6_ex.argtypes = [_u64p, _u64p, _L, _u64p, _L, _UL, _UL]
-        h.mpfft_mul6_ex.restype = ctypes.c_int
-        h.mpfft_mul6_device.argtypes = [_vp, _vp, _L, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-        h.mpfft_mul6_device.restype = ctypes.c_int
-        h.mpfft_workspace_bytes6.argtypes = [_L, _L, _UL, _UL]
-        h.mpfft_workspace_bytes6.restype = ctypes.c_size_t
-        h.mpfft_check_params6.argtypes = [_L, _L, _UL, _UL]
-        h.mpfft_check_params6.restype = ctypes.c_int
-        h.mpfft_plan_info6.argtypes = [_L, _L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
-        h.mpfft_plan_info6.restype = ctypes.c_int
-        if hasattr(h, "mpfft_sqr_ex"):   # MPFFT_VERSION 3 (older libraries in A/B runs lack them)
-            h.mpfft_sqr_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_sqr_ex.restype = ctypes.c_int
-            h.mpfft_sqr_auto.argtypes = [_u64p, _u64p, _L]
-            h.mpfft_sqr_auto.restype = ctypes.c_int
-            h.mpfft_sqr_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-            h.mpfft_sqr_device.restype = ctypes.c_int
-            h.mpfft_sqr_workspace_bytes.argtypes = [_L, _UL, _UL]
-            h.mpfft_sqr_workspace_bytes.restype = ctypes.c_size_t
-            h.mpfft_sqr_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_size_t)]
-            h.mpfft_sqr_workspace_layout.restype = ctypes.c_int
-            h.mpfft_sqr_stage.argtypes = [ctypes.c_int, _vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-            h.mpfft_sqr_stage.restype = ctypes.c_int
-            h.mpfft_sqr_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_char_p, ctypes.c_size_t]
-            h.mpfft_sqr_stage_kernels.restype = ctypes.c_int
-        if hasattr(h, "mpfft_mulmod_ex"):   # MPFFT_VERSION 4 (older libraries in A/B runs lack them)
-            _ulp = ctypes.POINTER(ctypes.c_ulong)
-            h.mpfft_mulmod_check_params.argtypes = [_L, _UL, _UL]
-            h.mpfft_mulmod_check_params.restype = ctypes.c_int
-            h.mpfft_mulmod_ex.argtypes = [_u64p, _u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_mulmod_ex.restype = ctypes.c_int
-            h.mpfft_sqrmod_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_sqrmod_ex.restype = ctypes.c_int
-            h.mpfft_mulmod_device.argtypes = [_vp, _vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-            h.mpfft_mulmod_device.restype = ctypes.c_int
-            h.mpfft_sqrmod_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-            h.mpfft_sqrmod_device.restype = ctypes.c_int
-            h.mpfft_mulmod_workspace_bytes.argtypes = [_L, _UL, _UL, ctypes.c_int]
-            h.mpfft_mulmod_workspace_bytes.restype = ctypes.c_size_t
-            h.mpfft_mulmod_plan_info.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
-            h.mpfft_mulmod_plan_info.restype = ctypes.c_int
-            h.mpfft_mulmod_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
-            h.mpfft_mulmod_workspace_layout.restype = ctypes.c_int
-            h.mpfft_mulmod_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _UL, _UL, ctypes.c_int, _vp,
-                                             ctypes.c_size_t, _vp]
-            h.mpfft_mulmod_stage.restype = ctypes.c_int
-            h.mpfft_mulmod_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-            h.mpfft_mulmod_stage_kernels.restype = ctypes.c_int
-            h.mpfft_mulmod_choose.argtypes = [_L, _ulp, _ulp]
-            h.mpfft_mulmod_choose.restype = ctypes.c_int
-            h.mpfft_mulmod_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
-            h.mpfft_mulmod_next_size.restype = ctypes.c_int
-        if hasattr(h, "mpfft_precomp_device"):   # MPFFT_VERSION 5 (older libraries in A/B runs lack them)
-            _sz = ctypes.c_size_t
-            h.mpfft_precomp_bytes.argtypes = [_L, _L, _UL, _UL]
-            h.mpfft_precomp_bytes.restype = _sz
-            h.mpfft_precomp_device.argtypes = [_vp, _sz, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_precomp_device.restype = ctypes.c_int
-            h.mpfft_mul_precomp_workspace_bytes.argtypes = [_L, _L, _UL, _UL]
-            h.mpfft_mul_precomp_workspace_bytes.restype = _sz
-            h.mpfft_mul_precomp_device.argtypes = [_vp, _vp, _L, _vp, _sz, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_mul_precomp_device.restype = ctypes.c_int
-            h.mpfft_precomp_stage_kernels.argtypes = [_L, _L, _UL, _UL, ctypes.c_char_p, _sz]
-            h.mpfft_precomp_stage_kernels.restype = ctypes.c_int
-            h.mpfft_precomp_stage.argtypes = [ctypes.c_int, _vp, _sz, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_precomp_stage.restype = ctypes.c_int
-            h.mpfft_mul_precomp_stage.argtypes = [ctypes.c_int, _vp, _vp, _sz, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_mul_precomp_stage.restype = ctypes.c_int
-            h.mpfft_precomp_create.argtypes = [ctypes.POINTER(_vp), _u64p, _L, _L, _UL, _UL]
-            h.mpfft_precomp_create.restype = ctypes.c_int
-            h.mpfft_mul_precomp_ex.argtypes = [_u64p, _u64p, _L, _vp]
-            h.mpfft_mul_precomp_ex.restype = ctypes.c_int
-            h.mpfft_precomp_destroy.argtypes = [_vp]
-            h.mpfft_precomp_destroy.restype = None
-        if hasattr(h, "mpfft_mulmodm1_ex"):   # MPFFT_VERSION 6 (older libraries in A/B runs lack them)
-            _ulp = ctypes.POINTER(ctypes.c_ulong)
-            _sz = ctypes.c_size_t
-            h.mpfft_mulmodm1_check_params.argtypes = [_L, _UL, _UL]
-            h.mpfft_mulmodm1_check_params.restype = ctypes.c_int
-            h.mpfft_mulmodm1_ex.argtypes = [_u64p, _u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_mulmodm1_ex.restype = ctypes.c_int
-            h.mpfft_sqrmodm1_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_sqrmodm1_ex.restype = ctypes.c_int
-            h.mpfft_mulmodm1_device.argtypes = [_vp, _vp, _vp, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_mulmodm1_device.restype = ctypes.c_int
-            h.mpfft_sqrmodm1_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_sqrmodm1_device.restype = ctypes.c_int
-            h.mpfft_mulmodm1_workspace_bytes.argtypes = [_L, _UL, _UL, ctypes.c_int]
-            h.mpfft_mulmodm1_workspace_bytes.restype = _sz
-            h.mpfft_mulmodm1_plan_info.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
-            h.mpfft_mulmodm1_plan_info.restype = ctypes.c_int
-            h.mpfft_mulmodm1_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.POINTER(_sz)]
-            h.mpfft_mulmodm1_workspace_layout.restype = ctypes.c_int
-            h.mpfft_mulmodm1_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _UL, _UL, ctypes.c_int, _vp, _sz, _vp]
-            h.mpfft_mulmodm1_stage.restype = ctypes.c_int
-            h.mpfft_mulmodm1_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.c_char_p, _sz]
-            h.mpfft_mulmodm1_stage_kernels.restype = ctypes.c_int
-            h.mpfft_mulmodm1_choose.argtypes = [_L, _ulp, _ulp]
-            h.mpfft_mulmodm1_choose.restype = ctypes.c_int
-            h.mpfft_mulmodm1_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
-            h.mpfft_mulmodm1_next_size.restype = ctypes.c_int
-            h.mpfft_mulmodm1_precomp_bytes.argtypes = [_L, _UL, _UL]
-            h.mpfft_mulmodm1_precomp_bytes.restype = _sz
-            h.mpfft_mulmodm1_precomp_device.argtypes = [_vp, _sz, _vp, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_mulmodm1_precomp_device.restype = ctypes.c_int
-            h.mpfft_mulmodm1_mul_precomp_device.argtypes = [_vp, _vp, _vp, _sz, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_mulmodm1_mul_precomp_device.restype = ctypes.c_int
-        if hasattr(h, "mpfft_mulmodw_ex"):   # MPFFT_VERSION 7 (older libraries in A/B runs lack them)
-            _ulp = ctypes.POINTER(ctypes.c_ulong)
-            h.mpfft_mulmodw_check_params.argtypes = [_L, _UL, _UL]
-            h.mpfft_mulmodw_check_params.restype = ctypes.c_int
-            h.mpfft_mulmodw_ex.argtypes = [_u64p, _u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_mulmodw_ex.restype = ctypes.c_int
-            h.mpfft_sqrmodw_ex.argtypes = [_u64p, _u64p, _L, _UL, _UL]
-            h.mpfft_sqrmodw_ex.restype = ctypes.c_int
-            h.mpfft_mulmodw_device.argtypes = [_vp, _vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-            h.mpfft_mulmodw_device.restype = ctypes.c_int
-            h.mpfft_sqrmodw_device.argtypes = [_vp, _vp, _L, _UL, _UL, _vp, ctypes.c_size_t, _vp]
-            h.mpfft_sqrmodw_device.restype = ctypes.c_int
-            h.mpfft_mulmodw_workspace_bytes.argtypes = [_L, _UL, _UL, ctypes.c_int]
-            h.mpfft_mulmodw_workspace_bytes.restype = ctypes.c_size_t
-            h.mpfft_mulmodw_plan_info.argtypes = [_L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
-            h.mpfft_mulmodw_plan_info.restype = ctypes.c_int
-            h.mpfft_mulmodw_workspace_layout.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]
-            h.mpfft_mulmodw_workspace_layout.restype = ctypes.c_int
-            h.mpfft_mulmodw_stage.argtypes = [ctypes.c_int, _vp, _vp, _vp, _L, _UL, _UL, ctypes.c_int, _vp,
-                                              ctypes.c_size_t, _vp]
-            h.mpfft_mulmodw_stage.restype = ctypes.c_int
-            h.mpfft_mulmodw_stage_kernels.argtypes = [_L, _UL, _UL, ctypes.c_int, ctypes.c_char_p, ctypes.c_size_t]
-            h.mpfft_mulmodw_stage_kernels.restype = ctypes.c_int
-            h.mpfft_mulmodw_choose.argtypes = [_L, _ulp, _ulp]
-            h.mpfft_mulmodw_choose.restype = ctypes.c_int
-            h.mpfft_mulmodw_next_size.argtypes = [_L, ctypes.POINTER(ctypes.c_long), _ulp, _ulp]
-            h.mpfft_mulmodw_next_size.restype = ctypes.c_int
-        if hasattr(h, "mpfft_dot_device"):   # MPFFT_VERSION 8 (older libraries in A/B runs lack them)
-            _ulp = ctypes.POINTER(ctypes.c_ulong)
-            _sz = ctypes.c_size_t
-            _pp = ctypes.POINTER(ctypes.c_void_p)
-            h.mpfft_dot_check_params.argtypes = [_L, _L, _L, _UL, _UL]
-            h.mpfft_dot_check_params.restype = ctypes.c_int
-            h.mpfft_dot_plan_info.argtypes = [_L, _L, _L, _UL, _UL, ctypes.POINTER(ctypes.c_long)]
-            h.mpfft_dot_plan_info.restype = ctypes.c_int
-            h.mpfft_dot_choose.argtypes = [_L, _L, _L, _ulp, _ulp]
-            h.mpfft_dot_choose.restype = ctypes.c_int
-            h.mpfft_dot_workspace_bytes.argtypes = [_L, _L, _L, _UL, _UL]
-            h.mpfft_dot_workspace_bytes.restype = _sz
-            h.mpfft_dot_workspace_layout.argtypes = [_L, _L, _L, _UL, _UL, ctypes.POINTER(_sz)]
-            h.mpfft_dot_workspace_layout.restype = ctypes.c_int
-            h.mpfft_dot_device.argtypes = [_vp, _L, _pp, _pp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_dot_device.restype = ctypes.c_int
-            h.mpfft_dot_ex.argtypes = [_u64p, _L, _pp, _pp, _L, _L, _UL, _UL]
-            h.mpfft_dot_ex.restype = ctypes.c_int
-            h.mpfft_dot_auto.argtypes = [_u64p, _L, _pp, _pp, _L, _L]
-            h.mpfft_dot_auto.restype = ctypes.c_int
-            h.mpfft_dot_stage_kernels.argtypes = [_L, _L, _L, _UL, _UL, ctypes.c_char_p, _sz]
-            h.mpfft_dot_stage_kernels.restype = ctypes.c_int
-            h.mpfft_dot_stage.argtypes = [ctypes.c_int, _L, _vp, _vp, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_dot_stage.restype = ctypes.c_int
-        if hasattr(h, "mpfft_sdot_device"):   # MPFFT_VERSION 9
-            _sz = ctypes.c_size_t
-            _pp = ctypes.POINTER(ctypes.c_void_p)
-            _U64 = ctypes.c_uint64
-            h.mpfft_sdot_check_params.argtypes = [_L, _U64, _L, _L, _UL, _UL]
-            h.mpfft_sdot_check_params.restype = ctypes.c_int
-            h.mpfft_sdot_workspace_bytes.argtypes = [_L, _L, _L, _UL, _UL]
-            h.mpfft_sdot_workspace_bytes.restype = _sz
-            h.mpfft_sdot_workspace_layout.argtypes = [_L, _L, _L, _UL, _UL, ctypes.POINTER(_sz)]
-            h.mpfft_sdot_workspace_layout.restype = ctypes.c_int
-            h.mpfft_sdot_device.argtypes = [_vp, _L, _U64, _pp, _pp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_sdot_device.restype = ctypes.c_int
-            h.mpfft_sdot_ex.argtypes = [_u64p, _L, _U64, _pp, _pp, _L, _L, _UL, _UL]
-            h.mpfft_sdot_ex.restype = ctypes.c_int
-            h.mpfft_sdot_auto.argtypes = [_u64p, _L, _U64, _pp, _pp, _L, _L]
-            h.mpfft_sdot_auto.restype = ctypes.c_int
-            h.mpfft_sdot_stage_kernels.argtypes = [_L, _U64, _L, _L, _UL, _UL, ctypes.c_char_p, _sz]
-            h.mpfft_sdot_stage_kernels.restype = ctypes.c_int
-            h.mpfft_sdot_stage.argtypes = [ctypes.c_int, _L, _vp, _vp, _vp, _L, _L, _UL, _UL, _vp, _sz, _vp]
-            h.mpfft_sdot_stage.restype = ctypes.c_int
+        for name, restype, argtypes in _signatures():
+            f = getattr(h, name, None)
+            if f is None:   # (older libraries in A/B runs through MPFFT_LIB lack the later versions' entries)
+                continue
+            f.restype, f.argtypes = restype, argtypes
         _lib = h
     return _lib
 
@@ -351,18 +184,44 @@ def _p(a):
     return a.ctypes.data_as(_u64p)
 
 
+_PLAN_KEYS = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
+_LAYOUT_KEYS = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
+
+
+def _plan_info(fn, what, *args):
+    """a *_plan_info entry's ten words as a dict, or MpfftError(what)"""
+    out = (ctypes.c_long * len(_PLAN_KEYS))()
+    rc = fn(*args, out)
+    if rc:
+        raise MpfftError(rc, what)
+    return dict(zip(_PLAN_KEYS, list(out)))
+
+
+def _layout(fn, what, keys, *args):
+    """a *_workspace_layout entry's words as a dict under `keys`"""
+    out = (ctypes.c_size_t * len(keys))()
+    rc = fn(*args, out)
+    if rc:
+        raise MpfftError(rc, what)
+    return dict(zip(keys, list(out)))
+
+
+def _kernel_names(fn, what, size, fields, *args):
+    """a *_stage_kernels entry's ';'-joined text (at most size bytes) as a dict under `fields`"""
+    buf = ctypes.create_string_buffer(size)
+    rc = fn(*args, buf, len(buf))
+    if rc:
+        raise MpfftError(rc, what)
+    return dict(zip(fields, buf.value.decode().split(";")))
+
+
 def check_params(n1, n2, depth, w):
     return lib().mpfft_check_params(n1, n2, depth, w)
 
 
 def plan_info(n1, n2, depth, w):
     """dict of the derived parameters (mul_fft.c:3193-3203) or MpfftError."""
-    out = (ctypes.c_long * 10)()
-    rc = lib().mpfft_plan_info(n1, n2, depth, w, out)
-    if rc:
-        raise MpfftError(rc, f"plan(n1={n1}, n2={n2}, depth={depth}, w={w})")
-    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
-    return dict(zip(keys, list(out)))
+    return _plan_info(lib().mpfft_plan_info, f"plan(n1={n1}, n2={n2}, depth={depth}, w={w})", n1, n2, depth, w)
 
 
 def workspace_bytes(n1, n2, depth, w):
@@ -417,12 +276,7 @@ def check_params6(n1, n2, depth, w):
 def plan_info6(n1, n2, depth, w):
     """derived parameters of new_mpn_mul6 (mul_fft.c:3575-3603): bits1 = (N - depth - 1)/2,
     trunc over a length-4n convolution"""
-    out = (ctypes.c_long * 10)()
-    rc = lib().mpfft_plan_info6(n1, n2, depth, w, out)
-    if rc:
-        raise MpfftError(rc, f"plan6(n1={n1}, n2={n2}, depth={depth}, w={w})")
-    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
-    return dict(zip(keys, list(out)))
+    return _plan_info(lib().mpfft_plan_info6, f"plan6(n1={n1}, n2={n2}, depth={depth}, w={w})", n1, n2, depth, w)
 
 
 def workspace_bytes6(n1, n2, depth, w):
@@ -509,21 +363,14 @@ STAGE_NAMES = ("fwd_columns", "fwd_rows", "pointwise", "inv_rows", "inv_columns"
 
 def stage_kernels(n1, n2, depth, w):
     """dict stage -> the kernel the library launches for it with these parameters"""
-    buf = ctypes.create_string_buffer(512)
-    rc = lib().mpfft_stage_kernels(n1, n2, depth, w, buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+    return _kernel_names(lib().mpfft_stage_kernels, "mpfft_stage_kernels", 512, STAGE_NAMES, n1, n2, depth, w)
 
 
 def inv_columns_schedule(n1, n2, depth, w):
     """The launches of the single-device truncated inverse column transform, in order (a host-side
     dry run: needs no GPU)."""
-    f = lib().mpfft_inv_columns_schedule
-    f.argtypes = [_L, _L, _UL, _UL, ctypes.c_char_p, ctypes.c_size_t]
-    f.restype = ctypes.c_int
     buf = ctypes.create_string_buffer(1 << 16)
-    rc = f(n1, n2, depth, w, buf, len(buf))
+    rc = lib().mpfft_inv_columns_schedule(n1, n2, depth, w, buf, len(buf))
     if rc:
         raise MpfftError(rc, "mpfft_inv_columns_schedule")
     return buf.value.decode().splitlines()
@@ -547,12 +394,7 @@ def profile_end():
 
 
 def workspace_layout(n1, n2, depth, w):
-    out = (ctypes.c_size_t * 8)()
-    rc = lib().mpfft_workspace_layout(n1, n2, depth, w, out)
-    if rc:
-        raise MpfftError(rc, "workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
-    return dict(zip(keys, list(out)))
+    return _layout(lib().mpfft_workspace_layout, "workspace_layout", _LAYOUT_KEYS, n1, n2, depth, w)
 
 
 def workspace_views(ws, n1, n2, depth, w):
@@ -624,20 +466,11 @@ def sqr_stage(which, d_a, d_r, n, depth, w, ws, stream=None):
 def sqr_stage_kernels(n, depth, w):
     """dict stage -> the kernel a square launches for it (the pointwise: k_pwsq<M>... or
     '<kernel> (B = A)')"""
-    buf = ctypes.create_string_buffer(512)
-    rc = lib().mpfft_sqr_stage_kernels(n, depth, w, buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_sqr_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+    return _kernel_names(lib().mpfft_sqr_stage_kernels, "mpfft_sqr_stage_kernels", 512, STAGE_NAMES, n, depth, w)
 
 
 def sqr_workspace_layout(n, depth, w):
-    out = (ctypes.c_size_t * 8)()
-    rc = lib().mpfft_sqr_workspace_layout(n, depth, w, out)
-    if rc:
-        raise MpfftError(rc, "sqr_workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
-    return dict(zip(keys, list(out)))
+    return _layout(lib().mpfft_sqr_workspace_layout, "sqr_workspace_layout", _LAYOUT_KEYS, n, depth, w)
 
 
 def sqr_workspace_views(ws, n, depth, w):
@@ -653,24 +486,55 @@ def sqr_workspace_views(ws, n, depth, w):
 
 
 # ---- sums of products (mpfft_dot_*, include/mpfft.h): r = sum_i a_i b_i with K forward transform
-# pairs and one inverse; the workspace has a third coefficient array C, the accumulator ----
+# pairs and one inverse; the workspace has a third coefficient array C, the accumulator.
+# Signed sums (mpfft_sdot_*): r = sum_i +-a_i b_i on the dot plan (dot_choose, dot_plan_info,
+# dot_max_limbs); the workspace is the dot's followed by the complement scratch and the accumulator D
+# of the subtracted b_i.  The sdot_* wrappers are the dot_* ones with the sign mask `neg` passed on. ----
 
 DOT_MAX = 64
 STAGE_ACC = 0x200   # dot_stage: or-ed onto STAGE_POINTWISE, C <- C + A B
+STAGE_SD_NEG = 10   # sdot_stage: d_a -> complement scratch, D <- d_b (| STAGE_ACC: D <- D + d_b)
+STAGE_SD_FIX = 11   # sdot_stage: d_r <- d_r + D - (D << 64 n1)
+SDOT_FIX_BLOCK = 4096   # limbs per block of the correction's carry chain (MPFFT_SDOT_FIX_BLOCK)
+_DOT_LAYOUT_KEYS = _LAYOUT_KEYS + ("digC", "topC", "cbC")
+
+
+def _neg_mask(neg):
+    """the sign mask as an int: an int is taken as it is, a sequence of booleans gives bit i = neg[i]"""
+    if isinstance(neg, (int, np.integer)) and not isinstance(neg, (bool, np.bool_)):
+        neg = int(neg)
+    else:
+        neg = sum(1 << i for i, x in enumerate(neg) if x)
+    if neg < 0 or neg >> 64:
+        raise ValueError("neg is a 64-bit mask")
+    return neg
+
+
+def _dot_entry(entry, neg):
+    """(the name, mpfft_dot_<entry> or with a mask mpfft_sdot_<entry>; that function; the mask argument, if any)"""
+    name = "%s_%s" % ("dot" if neg is None else "sdot", entry)
+    return name, getattr(lib(), "mpfft_" + name), () if neg is None else (_neg_mask(neg),)
+
+
+def sdot_to_int(limbs):
+    """the signed Python integer of a two's-complement little-endian limb array"""
+    limbs = np.ascontiguousarray(limbs, dtype=np.uint64)
+    v = int.from_bytes(limbs.tobytes(), "little")
+    return v - (1 << (64 * len(limbs))) if len(limbs) and int(limbs[-1]) >> 63 else v
 
 
 def dot_check_params(K, n1, n2, depth, w):
     return lib().mpfft_dot_check_params(K, n1, n2, depth, w)
 
 
+def sdot_check_params(K, neg, n1, n2, depth, w):
+    return lib().mpfft_sdot_check_params(K, _neg_mask(neg), n1, n2, depth, w)
+
+
 def dot_plan_info(K, n1, n2, depth, w):
     """plan_info of a K-term sum: bits1 = (N - depth - ceil(log2 K)) / 2 and what follows from it"""
-    out = (ctypes.c_long * 10)()
-    rc = lib().mpfft_dot_plan_info(K, n1, n2, depth, w, out)
-    if rc:
-        raise MpfftError(rc, f"dot plan(K={K}, n1={n1}, n2={n2}, depth={depth}, w={w})")
-    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
-    return dict(zip(keys, list(out)))
+    return _plan_info(lib().mpfft_dot_plan_info, f"dot plan(K={K}, n1={n1}, n2={n2}, depth={depth}, w={w})",
+                      K, n1, n2, depth, w)
 
 
 def dot_choose(K, n1, n2):
@@ -694,21 +558,33 @@ def dot_workspace_bytes(K, n1, n2, depth, w):
     return int(lib().mpfft_dot_workspace_bytes(K, n1, n2, depth, w))
 
 
-def alloc_workspace_dot(K, n1, n2, depth, w, device="cuda"):
+def sdot_workspace_bytes(K, n1, n2, depth, w):
+    return int(lib().mpfft_sdot_workspace_bytes(K, n1, n2, depth, w))
+
+
+def _alloc_workspace_dot(nb, what, K, n1, n2, depth, w, device):
     import torch
-    nb = dot_workspace_bytes(K, n1, n2, depth, w)
     if nb == 0:
-        raise MpfftError(dot_check_params(K, n1, n2, depth, w), "dot workspace")
+        raise MpfftError(dot_check_params(K, n1, n2, depth, w), what)
     return torch.empty(nb, dtype=torch.uint8, device=device)
 
 
+def alloc_workspace_dot(K, n1, n2, depth, w, device="cuda"):
+    return _alloc_workspace_dot(dot_workspace_bytes(K, n1, n2, depth, w), "dot workspace", K, n1, n2, depth, w, device)
+
+
+def alloc_workspace_sdot(K, n1, n2, depth, w, device="cuda"):
+    return _alloc_workspace_dot(sdot_workspace_bytes(K, n1, n2, depth, w), "sdot workspace", K, n1, n2, depth, w, device)
+
+
 def dot_workspace_layout(K, n1, n2, depth, w):
-    out = (ctypes.c_size_t * 11)()
-    rc = lib().mpfft_dot_workspace_layout(K, n1, n2, depth, w, out)
-    if rc:
-        raise MpfftError(rc, "dot_workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw", "digC", "topC", "cbC")
-    return dict(zip(keys, list(out)))
+    return _layout(lib().mpfft_dot_workspace_layout, "dot_workspace_layout", _DOT_LAYOUT_KEYS, K, n1, n2, depth, w)
+
+
+def sdot_workspace_layout(K, n1, n2, depth, w):
+    """dot_workspace_layout's entries, then "scratch" (the complement, n1 limbs) and "D" (n2 limbs)"""
+    return _layout(lib().mpfft_sdot_workspace_layout, "sdot_workspace_layout", _DOT_LAYOUT_KEYS + ("scratch", "D"),
+                   K, n1, n2, depth, w)
 
 
 def dot_workspace_views(ws, K, n1, n2, depth, w):
@@ -731,15 +607,26 @@ def _ptr_array(ts):
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
+def _dot_device(neg, d_r, d_as, d_bs, n1, n2, depth, w, ws, stream):
+    if len(d_as) != len(d_bs):
+        raise ValueError("as many a_i as b_i")
+    name, fn, mask = _dot_entry("device", neg)
+    rc = fn(_ptr(d_r), len(d_as), *mask, _ptr_array(d_as), _ptr_array(d_bs), n1, n2, depth, w, _ptr(ws), _nbytes(ws),
+            _stream(stream))
+    if rc:
+        raise MpfftError(rc, "mpfft_" + name)
+
+
 def dot_device(d_r, d_as, d_bs, n1, n2, depth, w, ws, stream=None):
     """d_r[:n1 + n2 + 1] = sum_i d_as[i][:n1] * d_bs[i][:n2], all tensors on the GPU (lists of K
     tensors; the same tensor may appear more than once); queued on `stream`, not synchronised."""
-    if len(d_as) != len(d_bs):
-        raise ValueError("as many a_i as b_i")
-    rc = lib().mpfft_dot_device(_ptr(d_r), len(d_as), _ptr_array(d_as), _ptr_array(d_bs), n1, n2, depth, w, _ptr(ws),
-                                ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_dot_device")
+    _dot_device(None, d_r, d_as, d_bs, n1, n2, depth, w, ws, stream)
+
+
+def sdot_device(d_r, d_as, d_bs, neg, n1, n2, depth, w, ws, stream=None):
+    """d_r[:n1 + n2 + 1] = sum_i +-d_as[i][:n1] * d_bs[i][:n2] in two's complement, term i subtracted
+    where neg (an int mask or a sequence of booleans) says so; as dot_device otherwise."""
+    _dot_device(neg, d_r, d_as, d_bs, n1, n2, depth, w, ws, stream)
 
 
 def _host_terms(a_list, b_list):
@@ -755,145 +642,75 @@ def _host_terms(a_list, b_list):
     return a_list, b_list, pa, pb, n1, n2
 
 
+def _dot(neg, a_list, b_list, depth, w):
+    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
+    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
+    name, fn, mask = _dot_entry("ex", neg)
+    rc = fn(_p(r), len(a_list), *mask, pa, pb, n1, n2, depth, w)
+    if rc:
+        raise MpfftError(rc, f"{name[:-3]}(K={len(a_list)}, n1={n1}, n2={n2}, depth={depth}, w={w})")
+    return r
+
+
 def dot(a_list, b_list, depth, w):
     """sum_i a_list[i] * b_list[i] as a new uint64 array of n1 + n2 + 1 limbs (host pointers, mpfft_dot_ex)"""
-    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
-    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
-    rc = lib().mpfft_dot_ex(_p(r), len(a_list), pa, pb, n1, n2, depth, w)
-    if rc:
-        raise MpfftError(rc, f"dot(K={len(a_list)}, n1={n1}, n2={n2}, depth={depth}, w={w})")
-    return r
-
-
-def dot_auto(a_list, b_list):
-    """dot() with (depth, w) from dot_choose()"""
-    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
-    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
-    rc = lib().mpfft_dot_auto(_p(r), len(a_list), pa, pb, n1, n2)
-    if rc:
-        raise MpfftError(rc, f"dot_auto(K={len(a_list)}, n1={n1}, n2={n2})")
-    return r
-
-
-def dot_stage(which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream=None):
-    """one stage for one term (d_a, d_b) on the K-term plan and workspace (tests)"""
-    rc = lib().mpfft_dot_stage(which, K, _ptr(d_a), _ptr(d_b), _ptr(d_r), n1, n2, depth, w, _ptr(ws),
-                               ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, f"mpfft_dot_stage({which})")
-
-
-def dot_stage_kernels(K, n1, n2, depth, w):
-    """dict stage -> the kernels a K-term sum launches for it (the pointwise: the first term's kernel
-    + the later terms')"""
-    buf = ctypes.create_string_buffer(640)
-    rc = lib().mpfft_dot_stage_kernels(K, n1, n2, depth, w, buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_dot_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
-
-
-# ---- signed sums of products (mpfft_sdot_*, include/mpfft.h): r = sum_i +-a_i b_i on the dot plan
-# (dot_choose, dot_plan_info, dot_max_limbs); the workspace is the dot's followed by the complement
-# scratch and the accumulator D of the subtracted b_i ----
-
-STAGE_SD_NEG = 10   # sdot_stage: d_a -> complement scratch, D <- d_b (| STAGE_ACC: D <- D + d_b)
-STAGE_SD_FIX = 11   # sdot_stage: d_r <- d_r + D - (D << 64 n1)
-SDOT_FIX_BLOCK = 4096   # limbs per block of the correction's carry chain (MPFFT_SDOT_FIX_BLOCK)
-
-
-def _neg_mask(neg):
-    """the sign mask as an int: an int is taken as it is, a sequence of booleans gives bit i = neg[i]"""
-    if isinstance(neg, (int, np.integer)) and not isinstance(neg, (bool, np.bool_)):
-        neg = int(neg)
-    else:
-        neg = sum(1 << i for i, x in enumerate(neg) if x)
-    if neg < 0 or neg >> 64:
-        raise ValueError("neg is a 64-bit mask")
-    return neg
-
-
-def sdot_to_int(limbs):
-    """the signed Python integer of a two's-complement little-endian limb array"""
-    limbs = np.ascontiguousarray(limbs, dtype=np.uint64)
-    v = int.from_bytes(limbs.tobytes(), "little")
-    return v - (1 << (64 * len(limbs))) if len(limbs) and int(limbs[-1]) >> 63 else v
-
-
-def sdot_check_params(K, neg, n1, n2, depth, w):
-    return lib().mpfft_sdot_check_params(K, _neg_mask(neg), n1, n2, depth, w)
-
-
-def sdot_workspace_bytes(K, n1, n2, depth, w):
-    return int(lib().mpfft_sdot_workspace_bytes(K, n1, n2, depth, w))
-
-
-def alloc_workspace_sdot(K, n1, n2, depth, w, device="cuda"):
-    import torch
-    nb = sdot_workspace_bytes(K, n1, n2, depth, w)
-    if nb == 0:
-        raise MpfftError(dot_check_params(K, n1, n2, depth, w), "sdot workspace")
-    return torch.empty(nb, dtype=torch.uint8, device=device)
-
-
-def sdot_workspace_layout(K, n1, n2, depth, w):
-    """dot_workspace_layout's entries, then "scratch" (the complement, n1 limbs) and "D" (n2 limbs)"""
-    out = (ctypes.c_size_t * 13)()
-    rc = lib().mpfft_sdot_workspace_layout(K, n1, n2, depth, w, out)
-    if rc:
-        raise MpfftError(rc, "sdot_workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw", "digC", "topC", "cbC", "scratch", "D")
-    return dict(zip(keys, list(out)))
-
-
-def sdot_device(d_r, d_as, d_bs, neg, n1, n2, depth, w, ws, stream=None):
-    """d_r[:n1 + n2 + 1] = sum_i +-d_as[i][:n1] * d_bs[i][:n2] in two's complement, term i subtracted
-    where neg (an int mask or a sequence of booleans) says so; as dot_device otherwise."""
-    if len(d_as) != len(d_bs):
-        raise ValueError("as many a_i as b_i")
-    rc = lib().mpfft_sdot_device(_ptr(d_r), len(d_as), _neg_mask(neg), _ptr_array(d_as), _ptr_array(d_bs), n1, n2, depth, w,
-                                 _ptr(ws), ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_sdot_device")
+    return _dot(None, a_list, b_list, depth, w)
 
 
 def sdot(a_list, b_list, neg, depth, w):
     """sum_i +-a_list[i] * b_list[i] as a new uint64 array of n1 + n2 + 1 limbs, two's complement
     (host pointers, mpfft_sdot_ex); sdot_to_int gives its signed value"""
+    return _dot(neg, a_list, b_list, depth, w)
+
+
+def _dot_auto(neg, a_list, b_list):
     a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
     r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
-    rc = lib().mpfft_sdot_ex(_p(r), len(a_list), _neg_mask(neg), pa, pb, n1, n2, depth, w)
+    name, fn, mask = _dot_entry("auto", neg)
+    rc = fn(_p(r), len(a_list), *mask, pa, pb, n1, n2)
     if rc:
-        raise MpfftError(rc, f"sdot(K={len(a_list)}, n1={n1}, n2={n2}, depth={depth}, w={w})")
+        raise MpfftError(rc, f"{name}(K={len(a_list)}, n1={n1}, n2={n2})")
     return r
+
+
+def dot_auto(a_list, b_list):
+    """dot() with (depth, w) from dot_choose()"""
+    return _dot_auto(None, a_list, b_list)
 
 
 def sdot_auto(a_list, b_list, neg):
     """sdot() with (depth, w) from dot_choose()"""
-    a_list, b_list, pa, pb, n1, n2 = _host_terms(a_list, b_list)
-    r = np.zeros(n1 + n2 + 1, dtype=np.uint64)
-    rc = lib().mpfft_sdot_auto(_p(r), len(a_list), _neg_mask(neg), pa, pb, n1, n2)
+    return _dot_auto(neg, a_list, b_list)
+
+
+def _dot_stage(name, which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream):
+    rc = getattr(lib(), "mpfft_" + name)(which, K, _ptr(d_a), _ptr(d_b), _ptr(d_r), n1, n2, depth, w, _ptr(ws), _nbytes(ws),
+                                         _stream(stream))
     if rc:
-        raise MpfftError(rc, f"sdot_auto(K={len(a_list)}, n1={n1}, n2={n2})")
-    return r
+        raise MpfftError(rc, f"mpfft_{name}({which})")
+
+
+def dot_stage(which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream=None):
+    """one stage for one term (d_a, d_b) on the K-term plan and workspace (tests)"""
+    _dot_stage("dot_stage", which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream)
 
 
 def sdot_stage(which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream=None):
     """one stage on the signed sum's workspace (tests): STAGE_SD_NEG, STAGE_SD_FIX, or a dot_stage stage"""
-    rc = lib().mpfft_sdot_stage(which, K, _ptr(d_a), _ptr(d_b), _ptr(d_r), n1, n2, depth, w, _ptr(ws),
-                                ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, f"mpfft_sdot_stage({which})")
+    _dot_stage("sdot_stage", which, K, d_a, d_b, d_r, n1, n2, depth, w, ws, stream)
+
+
+def dot_stage_kernels(K, n1, n2, depth, w):
+    """dict stage -> the kernels a K-term sum launches for it (the pointwise: the first term's kernel
+    + the later terms')"""
+    return _kernel_names(lib().mpfft_dot_stage_kernels, "mpfft_dot_stage_kernels", 640, STAGE_NAMES, K, n1, n2, depth, w)
 
 
 def sdot_stage_kernels(K, neg, n1, n2, depth, w):
     """dot_stage_kernels' dict; with a negative term fwd_columns starts with the pre-pass kernel and
     combine ends with the correction's"""
-    buf = ctypes.create_string_buffer(768)
-    rc = lib().mpfft_sdot_stage_kernels(K, _neg_mask(neg), n1, n2, depth, w, buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_sdot_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
+    return _kernel_names(lib().mpfft_sdot_stage_kernels, "mpfft_sdot_stage_kernels", 768, STAGE_NAMES,
+                         K, _neg_mask(neg), n1, n2, depth, w)
 
 
 # ---- multiplication by a precomputed operand (mpfft_precomp_*, mpfft_mul_precomp_*, include/mpfft.h):
@@ -951,11 +768,8 @@ PRECOMP_STAGE_NAMES = ("precomp",) + STAGE_NAMES
 def precomp_stage_kernels(n1, n2, depth, w):
     """dict: 'precomp' -> what writes the cache (k_pwsx<M>... or 'copy'), then stage -> the kernel a
     multiply against the cache launches (the pointwise: k_pwsp<M>... or '<kernel> (B cached)')"""
-    buf = ctypes.create_string_buffer(640)
-    rc = lib().mpfft_precomp_stage_kernels(n1, n2, depth, w, buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_precomp_stage_kernels")
-    return dict(zip(PRECOMP_STAGE_NAMES, buf.value.decode().split(";")))
+    return _kernel_names(lib().mpfft_precomp_stage_kernels, "mpfft_precomp_stage_kernels", 640, PRECOMP_STAGE_NAMES,
+                         n1, n2, depth, w)
 
 
 def precomp_stage(which, pre, d_i2, n1, n2, depth, w, ws, stream=None):
@@ -1019,394 +833,185 @@ def mul_precomp(i1, pre):
     return r
 
 
-# ---- products mod 2^B + 1, B = 64 L (mpfft_mulmod_*, include/mpfft.h): operands and result are
-# L + 1 limbs, fully reduced (0 <= a <= 2^B) ----
-
-def mulmod_check_params(L, depth, w):
-    return lib().mpfft_mulmod_check_params(L, depth, w)
-
-
-def mulmod(a, b, depth, w):
-    """a b mod 2^(64 L) + 1 for L + 1-limb fully reduced a, b: a new uint64 array of L + 1 limbs."""
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    b = np.ascontiguousarray(b, dtype=np.uint64)
-    if len(a) != len(b) or len(a) < 2:
-        raise ValueError("operands are L + 1 limbs each")
-    L = len(a) - 1
-    r = np.zeros(L + 1, dtype=np.uint64)
-    rc = lib().mpfft_mulmod_ex(_p(r), _p(a), _p(b), L, depth, w)
-    if rc:
-        raise MpfftError(rc, f"mulmod(L={L}, depth={depth}, w={w})")
-    return r
-
-
-def sqrmod(a, depth, w):
-    """a^2 mod 2^(64 L) + 1 (one forward transform)."""
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    if len(a) < 2:
-        raise ValueError("the operand is L + 1 limbs")
-    L = len(a) - 1
-    r = np.zeros(L + 1, dtype=np.uint64)
-    rc = lib().mpfft_sqrmod_ex(_p(r), _p(a), L, depth, w)
-    if rc:
-        raise MpfftError(rc, f"sqrmod(L={L}, depth={depth}, w={w})")
-    return r
-
-
-def mulmod_workspace_bytes(L, depth, w, sqr=False):
-    return int(lib().mpfft_mulmod_workspace_bytes(L, depth, w, int(bool(sqr))))
-
-
-def alloc_workspace_mulmod(L, depth, w, sqr=False, device="cuda"):
-    import torch
-    nb = mulmod_workspace_bytes(L, depth, w, sqr)
-    if nb == 0:
-        raise MpfftError(mulmod_check_params(L, depth, w), "mulmod workspace")
-    return torch.empty(nb, dtype=torch.uint8, device=device)
-
-
-def mulmod_device(d_r, d_a, d_b, L, depth, w, ws, stream=None):
-    """d_r[:L+1] = d_a d_b mod 2^(64 L) + 1 on the GPU; queued on `stream`, not synchronised.
-    d_r may not be an operand (it may be the next call's)."""
-    rc = lib().mpfft_mulmod_device(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws),
-                                   ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_mulmod_device")
-
-
-def sqrmod_device(d_r, d_a, L, depth, w, ws, stream=None):
-    rc = lib().mpfft_sqrmod_device(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws),
-                                   ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_sqrmod_device")
-
-
-def mulmod_plan_info(L, depth, w):
-    out = (ctypes.c_long * 10)()
-    rc = lib().mpfft_mulmod_plan_info(L, depth, w, out)
-    if rc:
-        raise MpfftError(rc, f"mulmod plan(L={L}, depth={depth}, w={w})")
-    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
-    return dict(zip(keys, list(out)))
-
-
-def mulmod_workspace_layout(L, depth, w, sqr=False):
-    out = (ctypes.c_size_t * 8)()
-    rc = lib().mpfft_mulmod_workspace_layout(L, depth, w, int(bool(sqr)), out)
-    if rc:
-        raise MpfftError(rc, "mulmod_workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
-    return dict(zip(keys, list(out)))
-
-
-def mulmod_workspace_views(ws, L, depth, w, sqr=False):
-    """(digA, topA, cbA) views into a mulmod workspace tensor (slot-major): limbs (slots, l) int64,
-    carry limbs int32, carry masks (slots, cbw) int64."""
-    import torch
-    P = mulmod_plan_info(L, depth, w)
-    lay = mulmod_workspace_layout(L, depth, w, sqr)
-    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
-    u8 = ws.view(torch.uint8)
-    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
-    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
-    cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
-    return dig, top, cb
-
-
-def mulmod_stage(which, d_a, d_b, d_r, L, depth, w, ws, sqr=False, stream=None):
-    rc = lib().mpfft_mulmod_stage(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, int(bool(sqr)), _ptr(ws),
-                                  ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, f"mpfft_mulmod_stage({which})")
-
-
-def mulmod_stage_kernels(L, depth, w, sqr=False):
-    """dict stage -> the kernel a product mod 2^(64 L) + 1 launches for it"""
-    buf = ctypes.create_string_buffer(512)
-    rc = lib().mpfft_mulmod_stage_kernels(L, depth, w, int(bool(sqr)), buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_mulmod_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
-
-
-def mulmod_choose(L):
-    """(depth, w) of least predicted time that are valid for this L."""
-    d, w = ctypes.c_ulong(), ctypes.c_ulong()
-    rc = lib().mpfft_mulmod_choose(L, ctypes.byref(d), ctypes.byref(w))
-    if rc:
-        raise MpfftError(rc, f"mulmod_choose(L={L})")
-    return int(d.value), int(w.value)
-
-
-def mulmod_next_size(min_L):
-    """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
-    L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
-    rc = lib().mpfft_mulmod_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
-    if rc:
-        raise MpfftError(rc, f"mulmod_next_size({min_L})")
-    return int(L.value), int(d.value), int(w.value)
-
-
-# ---- products mod 2^B + 1 with the low-word CRT (mpfft_mulmodw_*, include/mpfft.h): the mulmod
-# functions' mirrors, valid up to 2 bits1 + depth + 2 <= N + 32 (and from bits1 = 32 on) ----
+# ---- products modulo 2^B + 1 and 2^B - 1, B = 64 L (include/mpfft.h): three entry families with the
+# same wrappers, written once in _ModFamily and bound to their public names below ----
 STAGE_LOWCONV = 9   # mulmodw_stage: the low-word convolution d from the operands
+M1_MUL, M1_SQR, M1_PRE = 0, 1, 2   # mulmodm1's plan kinds: multiply, square, multiply against a cached operand
 
 
-def mulmodw_check_params(L, depth, w):
-    return lib().mpfft_mulmodw_check_params(L, depth, w)
+class _ModFamily:
+    """The wrappers of mpfft_<name>_* and the squares' mpfft_sqr<name[3:]>_*.
+    extra: operands and result are L + extra limbs; kind: what the plan entries' last argument is made
+    from (a flag, or one of M1_*); layout_keys: the words of workspace_layout; d_view: workspace_views
+    also returns the low-word convolution"""
+
+    def __init__(self, name, extra, kind, layout_keys, d_view=False):
+        self.name, self.sq, self.extra, self.kind, self.layout_keys, self.d_view = \
+            name, "sqr" + name[3:], extra, kind, layout_keys, d_view
+        self.limbs = "L + %d" % extra if extra else "L"
+
+    def _fn(self, entry, sq=False):
+        return getattr(lib(), "mpfft_%s_%s" % (self.sq if sq else self.name, entry))
+
+    def check_params(self, L, depth, w):
+        return self._fn("check_params")(L, depth, w)
+
+    def mul(self, a, b, depth, w):
+        """a b mod 2^(64 L) +- 1 as a new uint64 array (host pointers); mod 2^B + 1: L + 1-limb fully reduced
+        operands and result, mod 2^B - 1: L limbs, any operand value, the result fully reduced"""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        if len(a) != len(b) or len(a) < self.extra + 1:
+            raise ValueError("operands are %s limbs each" % self.limbs)
+        L = len(a) - self.extra
+        r = np.zeros(len(a), dtype=np.uint64)
+        rc = self._fn("ex")(_p(r), _p(a), _p(b), L, depth, w)
+        if rc:
+            raise MpfftError(rc, f"{self.name}(L={L}, depth={depth}, w={w})")
+        return r
+
+    def sqr(self, a, depth, w):
+        """a^2 mod 2^(64 L) +- 1 (one forward transform)."""
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        if len(a) < self.extra + 1:
+            raise ValueError("the operand is %s limbs" % self.limbs)
+        L = len(a) - self.extra
+        r = np.zeros(len(a), dtype=np.uint64)
+        rc = self._fn("ex", True)(_p(r), _p(a), L, depth, w)
+        if rc:
+            raise MpfftError(rc, f"{self.sq}(L={L}, depth={depth}, w={w})")
+        return r
+
+    def workspace_bytes(self, L, depth, w, kind=0):
+        return int(self._fn("workspace_bytes")(L, depth, w, self.kind(kind)))
+
+    def alloc_workspace(self, L, depth, w, kind=0, device="cuda"):
+        import torch
+        nb = self.workspace_bytes(L, depth, w, kind)
+        if nb == 0:   # (or 1: a kind the family does not have, on valid parameters)
+            raise MpfftError(self.check_params(L, depth, w) or 1, self.name + " workspace")
+        return torch.empty(nb, dtype=torch.uint8, device=device)
+
+    def device(self, d_r, d_a, d_b, L, depth, w, ws, stream=None):
+        """d_r = d_a d_b mod 2^(64 L) +- 1 on the GPU; queued on `stream`, not synchronised.
+        d_r may not be (mod 2^B - 1: overlap) an operand (it may be the next call's)."""
+        rc = self._fn("device")(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws), _nbytes(ws), _stream(stream))
+        if rc:
+            raise MpfftError(rc, "mpfft_%s_device" % self.name)
+
+    def sqr_device(self, d_r, d_a, L, depth, w, ws, stream=None):
+        rc = self._fn("device", True)(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws), _nbytes(ws), _stream(stream))
+        if rc:
+            raise MpfftError(rc, "mpfft_%s_device" % self.sq)
+
+    def plan_info(self, L, depth, w):
+        return _plan_info(self._fn("plan_info"), f"{self.name} plan(L={L}, depth={depth}, w={w})", L, depth, w)
+
+    def workspace_layout(self, L, depth, w, kind=0):
+        return _layout(self._fn("workspace_layout"), self.name + "_workspace_layout", self.layout_keys,
+                       L, depth, w, self.kind(kind))
+
+    def workspace_views(self, ws, L, depth, w, kind=0):
+        """(digA, topA, cbA) views into a workspace tensor (slot-major): limbs (slots, l) int64, carry
+        limbs int32, carry masks (slots, cbw) int64; mulmodw: and the low-word convolution d, (slots,)
+        int32 (the words mod 2^32)."""
+        import torch
+        P = self.plan_info(L, depth, w)
+        lay = self.workspace_layout(L, depth, w, kind)
+        slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
+        u8 = ws.view(torch.uint8)
+        dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
+        top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
+        cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
+        if not self.d_view:
+            return dig, top, cb
+        return dig, top, cb, u8[lay["d"]:lay["d"] + slots * 4].view(torch.int32)
+
+    def stage(self, which, d_a, d_b, d_r, L, depth, w, ws, kind=0, stream=None):
+        rc = self._fn("stage")(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, self.kind(kind), _ptr(ws),
+                               _nbytes(ws), _stream(stream))
+        if rc:
+            raise MpfftError(rc, f"mpfft_{self.name}_stage({which})")
+
+    def stage_kernels(self, L, depth, w, kind=0):
+        """dict stage -> the kernel a product mod 2^(64 L) +- 1 launches for it"""
+        return _kernel_names(self._fn("stage_kernels"), "mpfft_%s_stage_kernels" % self.name, 512, STAGE_NAMES,
+                             L, depth, w, self.kind(kind))
+
+    def choose(self, L):
+        """(depth, w) of least predicted time that are valid for this L."""
+        d, w = ctypes.c_ulong(), ctypes.c_ulong()
+        rc = self._fn("choose")(L, ctypes.byref(d), ctypes.byref(w))
+        if rc:
+            raise MpfftError(rc, f"{self.name}_choose(L={L})")
+        return int(d.value), int(w.value)
+
+    def next_size(self, min_L):
+        """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
+        L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
+        rc = self._fn("next_size")(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
+        if rc:
+            raise MpfftError(rc, f"{self.name}_next_size({min_L})")
+        return int(L.value), int(d.value), int(w.value)
 
 
-def mulmodw(a, b, depth, w):
-    """a b mod 2^(64 L) + 1 for L + 1-limb fully reduced a, b: a new uint64 array of L + 1 limbs."""
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    b = np.ascontiguousarray(b, dtype=np.uint64)
-    if len(a) != len(b) or len(a) < 2:
-        raise ValueError("operands are L + 1 limbs each")
-    L = len(a) - 1
-    r = np.zeros(L + 1, dtype=np.uint64)
-    rc = lib().mpfft_mulmodw_ex(_p(r), _p(a), _p(b), L, depth, w)
-    if rc:
-        raise MpfftError(rc, f"mulmodw(L={L}, depth={depth}, w={w})")
-    return r
+def _flag(sqr):
+    return int(bool(sqr))
 
 
-def sqrmodw(a, depth, w):
-    """a^2 mod 2^(64 L) + 1 (one forward transform)."""
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    if len(a) < 2:
-        raise ValueError("the operand is L + 1 limbs")
-    L = len(a) - 1
-    r = np.zeros(L + 1, dtype=np.uint64)
-    rc = lib().mpfft_sqrmodw_ex(_p(r), _p(a), L, depth, w)
-    if rc:
-        raise MpfftError(rc, f"sqrmodw(L={L}, depth={depth}, w={w})")
-    return r
+# mod 2^B + 1 (mpfft_mulmod_*): operands and result are L + 1 limbs, fully reduced (0 <= a <= 2^B); the last
+# argument of the plan entries is sqr
+_MULMOD = _ModFamily("mulmod", 1, _flag, _LAYOUT_KEYS)
+mulmod_check_params = _MULMOD.check_params
+mulmod = _MULMOD.mul
+sqrmod = _MULMOD.sqr
+mulmod_workspace_bytes = _MULMOD.workspace_bytes
+alloc_workspace_mulmod = _MULMOD.alloc_workspace
+mulmod_device = _MULMOD.device
+sqrmod_device = _MULMOD.sqr_device
+mulmod_plan_info = _MULMOD.plan_info
+mulmod_workspace_layout = _MULMOD.workspace_layout
+mulmod_workspace_views = _MULMOD.workspace_views
+mulmod_stage = _MULMOD.stage
+mulmod_stage_kernels = _MULMOD.stage_kernels
+mulmod_choose = _MULMOD.choose
+mulmod_next_size = _MULMOD.next_size
 
+# the same with the low-word CRT (mpfft_mulmodw_*): valid up to 2 bits1 + depth + 2 <= N + 32 (and from
+# bits1 = 32 on); one layout word and one view more, d
+_MULMODW = _ModFamily("mulmodw", 1, _flag, _LAYOUT_KEYS + ("d",), d_view=True)
+mulmodw_check_params = _MULMODW.check_params
+mulmodw = _MULMODW.mul
+sqrmodw = _MULMODW.sqr
+mulmodw_workspace_bytes = _MULMODW.workspace_bytes
+alloc_workspace_mulmodw = _MULMODW.alloc_workspace
+mulmodw_device = _MULMODW.device
+sqrmodw_device = _MULMODW.sqr_device
+mulmodw_plan_info = _MULMODW.plan_info
+mulmodw_workspace_layout = _MULMODW.workspace_layout
+mulmodw_workspace_views = _MULMODW.workspace_views
+mulmodw_stage = _MULMODW.stage
+mulmodw_stage_kernels = _MULMODW.stage_kernels
+mulmodw_choose = _MULMODW.choose
+mulmodw_next_size = _MULMODW.next_size
 
-def mulmodw_workspace_bytes(L, depth, w, sqr=False):
-    return int(lib().mpfft_mulmodw_workspace_bytes(L, depth, w, int(bool(sqr))))
-
-
-def alloc_workspace_mulmodw(L, depth, w, sqr=False, device="cuda"):
-    import torch
-    nb = mulmodw_workspace_bytes(L, depth, w, sqr)
-    if nb == 0:
-        raise MpfftError(mulmodw_check_params(L, depth, w), "mulmodw workspace")
-    return torch.empty(nb, dtype=torch.uint8, device=device)
-
-
-def mulmodw_device(d_r, d_a, d_b, L, depth, w, ws, stream=None):
-    """d_r[:L+1] = d_a d_b mod 2^(64 L) + 1 on the GPU; queued on `stream`, not synchronised.
-    d_r may not be an operand (it may be the next call's)."""
-    rc = lib().mpfft_mulmodw_device(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws),
-                                    ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_mulmodw_device")
-
-
-def sqrmodw_device(d_r, d_a, L, depth, w, ws, stream=None):
-    rc = lib().mpfft_sqrmodw_device(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws),
-                                    ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_sqrmodw_device")
-
-
-def mulmodw_plan_info(L, depth, w):
-    out = (ctypes.c_long * 10)()
-    rc = lib().mpfft_mulmodw_plan_info(L, depth, w, out)
-    if rc:
-        raise MpfftError(rc, f"mulmodw plan(L={L}, depth={depth}, w={w})")
-    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
-    return dict(zip(keys, list(out)))
-
-
-def mulmodw_workspace_layout(L, depth, w, sqr=False):
-    out = (ctypes.c_size_t * 9)()
-    rc = lib().mpfft_mulmodw_workspace_layout(L, depth, w, int(bool(sqr)), out)
-    if rc:
-        raise MpfftError(rc, "mulmodw_workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw", "d")
-    return dict(zip(keys, list(out)))
-
-
-def mulmodw_workspace_views(ws, L, depth, w, sqr=False):
-    """(digA, topA, cbA, d) views into a mulmodw workspace tensor (slot-major): limbs (slots, l) int64,
-    carry limbs int32, carry masks (slots, cbw) int64, and the low-word convolution d, (slots,) int32
-    (the words mod 2^32)."""
-    import torch
-    P = mulmodw_plan_info(L, depth, w)
-    lay = mulmodw_workspace_layout(L, depth, w, sqr)
-    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
-    u8 = ws.view(torch.uint8)
-    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
-    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
-    cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
-    d = u8[lay["d"]:lay["d"] + slots * 4].view(torch.int32)
-    return dig, top, cb, d
-
-
-def mulmodw_stage(which, d_a, d_b, d_r, L, depth, w, ws, sqr=False, stream=None):
-    rc = lib().mpfft_mulmodw_stage(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, int(bool(sqr)), _ptr(ws),
-                                   ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, f"mpfft_mulmodw_stage({which})")
-
-
-def mulmodw_stage_kernels(L, depth, w, sqr=False):
-    """dict stage -> the kernel a product mod 2^(64 L) + 1 launches for it"""
-    buf = ctypes.create_string_buffer(512)
-    rc = lib().mpfft_mulmodw_stage_kernels(L, depth, w, int(bool(sqr)), buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_mulmodw_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
-
-
-def mulmodw_choose(L):
-    """(depth, w) of least predicted time that are valid for this L."""
-    d, w = ctypes.c_ulong(), ctypes.c_ulong()
-    rc = lib().mpfft_mulmodw_choose(L, ctypes.byref(d), ctypes.byref(w))
-    if rc:
-        raise MpfftError(rc, f"mulmodw_choose(L={L})")
-    return int(d.value), int(w.value)
-
-
-def mulmodw_next_size(min_L):
-    """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
-    L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
-    rc = lib().mpfft_mulmodw_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
-    if rc:
-        raise MpfftError(rc, f"mulmodw_next_size({min_L})")
-    return int(L.value), int(d.value), int(w.value)
-
-
-# ---- products mod 2^B - 1, B = 64 L (mpfft_mulmodm1_*, include/mpfft.h): operands and result are
-# L limbs; any operand value is valid, the result is fully reduced (never all-ones) ----
-M1_MUL, M1_SQR, M1_PRE = 0, 1, 2   # plan kinds: multiply, square, multiply against a cached operand
-
-
-def mulmodm1_check_params(L, depth, w):
-    return lib().mpfft_mulmodm1_check_params(L, depth, w)
-
-
-def mulmodm1(a, b, depth, w):
-    """a b mod 2^(64 L) - 1 for L-limb a, b: a new uint64 array of L limbs, fully reduced."""
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    b = np.ascontiguousarray(b, dtype=np.uint64)
-    if len(a) != len(b) or len(a) < 1:
-        raise ValueError("operands are L limbs each")
-    L = len(a)
-    r = np.zeros(L, dtype=np.uint64)
-    rc = lib().mpfft_mulmodm1_ex(_p(r), _p(a), _p(b), L, depth, w)
-    if rc:
-        raise MpfftError(rc, f"mulmodm1(L={L}, depth={depth}, w={w})")
-    return r
-
-
-def sqrmodm1(a, depth, w):
-    """a^2 mod 2^(64 L) - 1 (one forward transform)."""
-    a = np.ascontiguousarray(a, dtype=np.uint64)
-    if len(a) < 1:
-        raise ValueError("the operand is L limbs")
-    L = len(a)
-    r = np.zeros(L, dtype=np.uint64)
-    rc = lib().mpfft_sqrmodm1_ex(_p(r), _p(a), L, depth, w)
-    if rc:
-        raise MpfftError(rc, f"sqrmodm1(L={L}, depth={depth}, w={w})")
-    return r
-
-
-def mulmodm1_workspace_bytes(L, depth, w, kind=M1_MUL):
-    return int(lib().mpfft_mulmodm1_workspace_bytes(L, depth, w, int(kind)))
-
-
-def alloc_workspace_mulmodm1(L, depth, w, kind=M1_MUL, device="cuda"):
-    import torch
-    nb = mulmodm1_workspace_bytes(L, depth, w, kind)
-    if nb == 0:
-        raise MpfftError(mulmodm1_check_params(L, depth, w) or 1, "mulmodm1 workspace")
-    return torch.empty(nb, dtype=torch.uint8, device=device)
-
-
-def mulmodm1_device(d_r, d_a, d_b, L, depth, w, ws, stream=None):
-    """d_r[:L] = d_a d_b mod 2^(64 L) - 1 on the GPU; queued on `stream`, not synchronised.
-    d_r may not overlap an operand (it may be the next call's)."""
-    rc = lib().mpfft_mulmodm1_device(_ptr(d_r), _ptr(d_a), _ptr(d_b), L, depth, w, _ptr(ws),
-                                     ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_mulmodm1_device")
-
-
-def sqrmodm1_device(d_r, d_a, L, depth, w, ws, stream=None):
-    rc = lib().mpfft_sqrmodm1_device(_ptr(d_r), _ptr(d_a), L, depth, w, _ptr(ws),
-                                     ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, "mpfft_sqrmodm1_device")
-
-
-def mulmodm1_plan_info(L, depth, w):
-    out = (ctypes.c_long * 10)()
-    rc = lib().mpfft_mulmodm1_plan_info(L, depth, w, out)
-    if rc:
-        raise MpfftError(rc, f"mulmodm1 plan(L={L}, depth={depth}, w={w})")
-    keys = ("n", "l", "NC", "j1", "j2", "trunc", "bits1", "NR", "tpb", "U")
-    return dict(zip(keys, list(out)))
-
-
-def mulmodm1_workspace_layout(L, depth, w, kind=M1_MUL):
-    out = (ctypes.c_size_t * 8)()
-    rc = lib().mpfft_mulmodm1_workspace_layout(L, depth, w, int(kind), out)
-    if rc:
-        raise MpfftError(rc, "mulmodm1_workspace_layout")
-    keys = ("digA", "topA", "cbA", "digB", "topB", "cbB", "slots", "cbw")
-    return dict(zip(keys, list(out)))
-
-
-def mulmodm1_workspace_views(ws, L, depth, w, kind=M1_MUL):
-    """(digA, topA, cbA) views into a mulmodm1 workspace tensor (slot-major): limbs (slots, l) int64,
-    carry limbs int32, carry masks (slots, cbw) int64."""
-    import torch
-    P = mulmodm1_plan_info(L, depth, w)
-    lay = mulmodm1_workspace_layout(L, depth, w, kind)
-    slots, l, cbw = lay["slots"], P["l"], lay["cbw"]
-    u8 = ws.view(torch.uint8)
-    dig = u8[lay["digA"]:lay["digA"] + slots * l * 8].view(torch.int64).view(slots, l)
-    top = u8[lay["topA"]:lay["topA"] + slots * 4].view(torch.int32)
-    cb = u8[lay["cbA"]:lay["cbA"] + slots * cbw * 8].view(torch.int64).view(slots, cbw)
-    return dig, top, cb
-
-
-def mulmodm1_stage(which, d_a, d_b, d_r, L, depth, w, ws, kind=M1_MUL, stream=None):
-    rc = lib().mpfft_mulmodm1_stage(which, _ptr(d_a), _ptr(d_b), _ptr(d_r), L, depth, w, int(kind), _ptr(ws),
-                                    ws.numel() * ws.element_size(), _stream(stream))
-    if rc:
-        raise MpfftError(rc, f"mpfft_mulmodm1_stage({which})")
-
-
-def mulmodm1_stage_kernels(L, depth, w, kind=M1_MUL):
-    """dict stage -> the kernel a product mod 2^(64 L) - 1 launches for it"""
-    buf = ctypes.create_string_buffer(512)
-    rc = lib().mpfft_mulmodm1_stage_kernels(L, depth, w, int(kind), buf, len(buf))
-    if rc:
-        raise MpfftError(rc, "mpfft_mulmodm1_stage_kernels")
-    return dict(zip(STAGE_NAMES, buf.value.decode().split(";")))
-
-
-def mulmodm1_choose(L):
-    """(depth, w) of least predicted time that are valid for this L."""
-    d, w = ctypes.c_ulong(), ctypes.c_ulong()
-    rc = lib().mpfft_mulmodm1_choose(L, ctypes.byref(d), ctypes.byref(w))
-    if rc:
-        raise MpfftError(rc, f"mulmodm1_choose(L={L})")
-    return int(d.value), int(w.value)
-
-
-def mulmodm1_next_size(min_L):
-    """(L, depth, w): an efficient modulus size L >= min_L and its parameters."""
-    L, d, w = ctypes.c_long(), ctypes.c_ulong(), ctypes.c_ulong()
-    rc = lib().mpfft_mulmodm1_next_size(min_L, ctypes.byref(L), ctypes.byref(d), ctypes.byref(w))
-    if rc:
-        raise MpfftError(rc, f"mulmodm1_next_size({min_L})")
-    return int(L.value), int(d.value), int(w.value)
+# mod 2^B - 1 (mpfft_mulmodm1_*): operands and result are L limbs; any operand value is valid, the result is
+# fully reduced (never all-ones); the last argument of the plan entries is a kind M1_*
+_MULMODM1 = _ModFamily("mulmodm1", 0, int, _LAYOUT_KEYS)
+mulmodm1_check_params = _MULMODM1.check_params
+mulmodm1 = _MULMODM1.mul
+sqrmodm1 = _MULMODM1.sqr
+mulmodm1_workspace_bytes = _MULMODM1.workspace_bytes
+alloc_workspace_mulmodm1 = _MULMODM1.alloc_workspace
+mulmodm1_device = _MULMODM1.device
+sqrmodm1_device = _MULMODM1.sqr_device
+mulmodm1_plan_info = _MULMODM1.plan_info
+mulmodm1_workspace_layout = _MULMODM1.workspace_layout
+mulmodm1_workspace_views = _MULMODM1.workspace_views
+mulmodm1_stage = _MULMODM1.stage
+mulmodm1_stage_kernels = _MULMODM1.stage_kernels
+mulmodm1_choose = _MULMODM1.choose
+mulmodm1_next_size = _MULMODM1.next_size
 
 
 def mulmodm1_precomp_bytes(L, depth, w):

@@ -488,6 +488,72 @@ static void layout_out(const Plan &P, size_t *out)
     out[6] = P.slots; out[7] = (size_t)cb_words((int)P.l);
 }
 
+// The plan queries of every entry family, behind its make_plan_*: rc is that call's status, P the plan it
+// filled (read only where rc is 0).
+static size_t bytes_or_0(int rc, const Plan &P) { return rc ? 0 : P.bytes; }
+static int plan_info_out(int rc, const Plan &P, long *out)
+{
+    if (!rc) plan_info_out(P, out);
+    return rc;
+}
+static int layout_out(int rc, const Plan &P, size_t *out)
+{
+    if (!rc) layout_out(P, out);
+    return rc;
+}
+static int stage_names_out(int rc, const Plan &P, char *buf, size_t len)
+{
+    return rc ? rc : copy_out(stage_kernel_names(P), buf, len);
+}
+
+// The workspace precondition of a device or stage entry, checked behind the plan (else MPFFT_ENOMEM); the
+// entry is about to launch
+static bool ws_ok(const void *d_ws, size_t ws_bytes, size_t need)
+{
+    if (!d_ws || ws_bytes < need) return false;
+    (void)hipGetLastError();  // clear a sticky error left by another library in this process
+    return true;
+}
+// ... and that of a cache of operand 2: it holds the plan's forward transform (else MPFFT_ENOMEM)
+static bool pre_ok(const void *d_pre, size_t pre_bytes, const Plan &P)
+{
+    return d_pre && pre_bytes >= plan_pre_bytes(P);
+}
+
+// The (depth, w) grid every chooser walks: depth 2 .. 24 and w = 1, 2, 4 .. 4096 with whole-limb coefficients
+// of at most 4096 limbs.  make(&P, depth, w) builds a candidate's plan; *best is the valid one of least
+// choose_cost, the first of equals.  False if no candidate is valid.
+template <typename Make>
+static bool search_grid(Plan *best, Make make)
+{
+    double cost = -1.0;
+    for (unsigned long d = 2; d <= 24; ++d)
+        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
+            const unsigned long long N = (1ull << d) * wv;
+            if (N % 64) continue;
+            if (N / 64 > 4096) break;
+            Plan P;
+            if (make(&P, d, wv)) continue;
+            const double c = choose_cost(P);
+            if (cost < 0 || c < cost) {
+                cost = c;
+                *best = P;
+            }
+        }
+    return cost >= 0;
+}
+
+// mpfft_choose's and mpfft_dot_choose's pick: that plan's (depth, w), or MPFFT_ETOOBIG
+template <typename Make>
+static int choose_on_grid(unsigned long *depth, unsigned long *w, Make make)
+{
+    Plan best;
+    if (!search_grid(&best, make)) return MPFFT_ETOOBIG;
+    *depth = (unsigned long)best.depth;
+    *w = (unsigned long)best.w;
+    return MPFFT_OK;
+}
+
 // One single-GPU stage (device pointers) on plan P; `ws` has P's workspace layout.  A squaring
 // plan's forward stages run operand 0 alone.
 static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const uint64_t *d_i2, uint64_t *d_r,
@@ -497,8 +563,7 @@ static int single_stage(const Plan &P, int stage, const uint64_t *d_i1, const ui
     stage &= ~MPFFT_STAGE_DRIVEN;
     if (driven && stage != MPFFT_STAGE_INV_ROWS && stage != MPFFT_STAGE_INV_COLUMNS && stage != MPFFT_STAGE_SCALE)
         return MPFFT_EINVAL;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
+    if (!ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
     X.use_pre(d_pre);
@@ -629,37 +694,38 @@ int mpfft_check_params(long n1, long n2, unsigned long depth, unsigned long w)
 size_t mpfft_workspace_bytes(long n1, long n2, unsigned long depth, unsigned long w)
 {
     Plan P;
-    if (make_plan(&P, n1, n2, depth, w)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan(&P, n1, n2, depth, w), P);
 }
 
 int mpfft_workspace_layout(long n1, long n2, unsigned long depth, unsigned long w, size_t *out)
 {
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w);
-    if (rc) return rc;
-    layout_out(P, out);
-    return MPFFT_OK;
+    return layout_out(make_plan(&P, n1, n2, depth, w), P, out);
 }
 
 int mpfft_plan_info(long n1, long n2, unsigned long depth, unsigned long w, long *out)
 {
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w);
+    return plan_info_out(make_plan(&P, n1, n2, depth, w), P, out);
+}
+
+// The multiply's driver on plan P (status rc) and the caller's workspace: the device entries of the plain,
+// sqrt2, squaring, cached-operand and cyclic plans.  d_pre: the cache a Plan::pre plan reads, or with pre_make
+// the one the multiply's plan writes.
+static int device_run(int rc, const Plan &P, uint64_t *d_r, const uint64_t *d_i1, const uint64_t *d_i2, void *d_ws,
+                      size_t ws_bytes, void *stream, const void *d_pre = nullptr, size_t pre_bytes = 0, bool pre_make = false)
+{
     if (rc) return rc;
-    plan_info_out(P, out);
-    return MPFFT_OK;
+    if ((P.pre || pre_make) && !pre_ok(d_pre, pre_bytes, P)) return MPFFT_ENOMEM;
+    if (!ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
+    return run_all(P, d_r, d_i1, d_i2, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre, pre_make);
 }
 
 int mpfft_mul_device(uint64_t *d_r, const uint64_t *d_i1, long n1, const uint64_t *d_i2, long n2,
                      unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();  // clear a sticky error left by another library in this process
-    return run_all(P, d_r, d_i1, d_i2, (unsigned char *)d_ws, (hipStream_t)stream);
+    return device_run(make_plan(&P, n1, n2, depth, w), P, d_r, d_i1, d_i2, d_ws, ws_bytes, stream);
 }
 
 // stage entry points (device pointers), used by the stage-parity tests and the
@@ -869,26 +935,44 @@ static int ensure_buf(void **p, size_t *have, size_t need)
     return MPFFT_OK;
 }
 
+// One host-pointer call on the calling thread's device: open() finds the device's context, holds its lock
+// until the call returns, makes the context's stream on first use and grows its ws and io buffers to the
+// sizes stated.  copy: the copy stream and its event too.  on_dev >= 0: MPFFT_EINVAL on any other device.
+namespace {
+struct HostCall {
+    DevCtx *C = nullptr;
+    int dev = 0;
+    std::unique_lock<std::mutex> lk;
+    int open(size_t ws_bytes, size_t io_bytes, bool copy = false, int on_dev = -1)
+    {
+        int ndev = 0, rc;
+        (void)hipGetLastError();
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
+        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
+        if (on_dev >= 0 && dev != on_dev) return MPFFT_EINVAL;
+        C = &g_dev[dev];
+        lk = std::unique_lock<std::mutex>(C->mu);
+        if (!C->stream) HIPCHK(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking));
+        if (copy) {
+            if (!C->copy) HIPCHK(hipStreamCreateWithFlags(&C->copy, hipStreamNonBlocking));
+            if (!C->ready) HIPCHK(hipEventCreateWithFlags(&C->ready, hipEventDisableTiming));
+        }
+        if ((rc = ensure_buf((void **)&C->ws, &C->ws_bytes, ws_bytes))) return rc;
+        return ensure_buf((void **)&C->io, &C->io_bytes, io_bytes);
+    }
+};
+}  // namespace
+
 // Host operands on the calling thread's device: io holds the operands and, behind them, the
 // n1 + n2 result limbs.  A squaring plan (i2 == i1, n2 == n1) copies its one operand on the
 // context's stream and needs no copy stream and no event.
 static int mul_host(const Plan &P, uint64_t *r1, const uint64_t *i1, long n1, const uint64_t *i2, long n2)
 {
     int rc;
-    (void)hipGetLastError();
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
-    DevCtx &C = g_dev[dev];
-    std::lock_guard<std::mutex> lk(C.mu);
-    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
-    if (!P.sqr) {
-        if (!C.copy) HIPCHK(hipStreamCreateWithFlags(&C.copy, hipStreamNonBlocking));
-        if (!C.ready) HIPCHK(hipEventCreateWithFlags(&C.ready, hipEventDisableTiming));
-    }
+    HostCall H;
     const long nin = P.sqr ? n1 : n1 + n2;
-    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
-    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, (size_t)(nin + n1 + n2) * 8))) return rc;
+    if ((rc = H.open(P.bytes, (size_t)(nin + n1 + n2) * 8, !P.sqr))) return rc;
+    DevCtx &C = *H.C;
     u64 *d_i1 = C.io, *d_i2 = P.sqr ? d_i1 : d_i1 + n1, *d_r = C.io + nin;
     HIPCHK(hipMemcpyAsync(d_i1, i1, (size_t)n1 * 8, hipMemcpyHostToDevice, C.stream));
     HostB hb{P.sqrt2 || P.sqr ? nullptr : i2, C.copy, C.ready};
@@ -933,28 +1017,20 @@ int mpfft_check_params6(long n1, long n2, unsigned long depth, unsigned long w)
 size_t mpfft_workspace_bytes6(long n1, long n2, unsigned long depth, unsigned long w)
 {
     Plan P;
-    if (make_plan(&P, n1, n2, depth, w, true)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan(&P, n1, n2, depth, w, true), P);
 }
 
 int mpfft_plan_info6(long n1, long n2, unsigned long depth, unsigned long w, long *out)
 {
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w, true);
-    if (rc) return rc;
-    plan_info_out(P, out);
-    return MPFFT_OK;
+    return plan_info_out(make_plan(&P, n1, n2, depth, w, true), P, out);
 }
 
 int mpfft_mul6_device(uint64_t *d_r, const uint64_t *d_i1, long n1, const uint64_t *d_i2, long n2,
                       unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w, true);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_all(P, d_r, d_i1, d_i2, (unsigned char *)d_ws, (hipStream_t)stream);
+    return device_run(make_plan(&P, n1, n2, depth, w, true), P, d_r, d_i1, d_i2, d_ws, ws_bytes, stream);
 }
 
 int mpfft_mul6_ex(uint64_t *r1, const uint64_t *i1, long n1, const uint64_t *i2, long n2, unsigned long depth,
@@ -980,28 +1056,20 @@ void new_mpn_mul6(mp_limb_t *r1, mp_limb_t *i1, mp_size_t n1, mp_limb_t *i2, mp_
 size_t mpfft_sqr_workspace_bytes(long n, unsigned long depth, unsigned long w)
 {
     Plan P;
-    if (make_plan_sqr(&P, n, depth, w)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan_sqr(&P, n, depth, w), P);
 }
 
 int mpfft_sqr_workspace_layout(long n, unsigned long depth, unsigned long w, size_t *out)
 {
     Plan P;
-    int rc = make_plan_sqr(&P, n, depth, w);
-    if (rc) return rc;
-    layout_out(P, out);
-    return MPFFT_OK;
+    return layout_out(make_plan_sqr(&P, n, depth, w), P, out);
 }
 
 int mpfft_sqr_device(uint64_t *d_r, const uint64_t *d_a, long n, unsigned long depth, unsigned long w,
                      void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan_sqr(&P, n, depth, w);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_all(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream);
+    return device_run(make_plan_sqr(&P, n, depth, w), P, d_r, d_a, d_a, d_ws, ws_bytes, stream);
 }
 
 int mpfft_sqr_stage(int stage, const uint64_t *d_a, uint64_t *d_r, long n, unsigned long depth,
@@ -1016,9 +1084,7 @@ int mpfft_sqr_stage(int stage, const uint64_t *d_a, uint64_t *d_r, long n, unsig
 int mpfft_sqr_stage_kernels(long n, unsigned long depth, unsigned long w, char *buf, size_t len)
 {
     Plan P;
-    int rc = make_plan_sqr(&P, n, depth, w);
-    if (rc) return rc;
-    return copy_out(stage_kernel_names(P), buf, len);
+    return stage_names_out(make_plan_sqr(&P, n, depth, w), P, buf, len);
 }
 
 // host-pointer square: never routed by mpfft_set_devices
@@ -1048,31 +1114,20 @@ int mpfft_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t *d_i2, lo
                          unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_all(P, nullptr, nullptr, d_i2, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre, true);
+    return device_run(make_plan(&P, n1, n2, depth, w), P, nullptr, nullptr, d_i2, d_ws, ws_bytes, stream, d_pre, pre_bytes, true);
 }
 
 size_t mpfft_mul_precomp_workspace_bytes(long n1, long n2, unsigned long depth, unsigned long w)
 {
     Plan P;
-    if (make_plan_pre(&P, n1, n2, depth, w)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan_pre(&P, n1, n2, depth, w), P);
 }
 
 int mpfft_mul_precomp_device(uint64_t *d_r, const uint64_t *d_i1, long n1, const void *d_pre, size_t pre_bytes, long n2,
                              unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan_pre(&P, n1, n2, depth, w);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_all(P, d_r, d_i1, d_i1, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre);
+    return device_run(make_plan_pre(&P, n1, n2, depth, w), P, d_r, d_i1, d_i1, d_ws, ws_bytes, stream, d_pre, pre_bytes);
 }
 
 int mpfft_precomp_stage_kernels(long n1, long n2, unsigned long depth, unsigned long w, char *buf, size_t len)
@@ -1091,9 +1146,8 @@ int mpfft_precomp_stage(int stage, void *d_pre, size_t pre_bytes, const uint64_t
     if (rc) return rc;
     if (stage != MPFFT_STAGE_FWD_COLUMNS && stage != MPFFT_STAGE_FWD_ROWS && stage != MPFFT_STAGE_PRE_STORE)
         return MPFFT_EINVAL;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (stage == MPFFT_STAGE_PRE_STORE && (!d_pre || pre_bytes < plan_pre_bytes(P))) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
+    if (stage == MPFFT_STAGE_PRE_STORE && !pre_ok(d_pre, pre_bytes, P)) return MPFFT_ENOMEM;
+    if (!ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
     X.use_pre(d_pre);
@@ -1109,7 +1163,7 @@ int mpfft_mul_precomp_stage(int stage, const uint64_t *d_i1, const void *d_pre, 
     Plan P;
     int rc = make_plan_pre(&P, n1, n2, depth, w);
     if (rc) return rc;
-    if ((stage & ~MPFFT_STAGE_DRIVEN) == MPFFT_STAGE_POINTWISE && (!d_pre || pre_bytes < plan_pre_bytes(P))) return MPFFT_ENOMEM;
+    if ((stage & ~MPFFT_STAGE_DRIVEN) == MPFFT_STAGE_POINTWISE && !pre_ok(d_pre, pre_bytes, P)) return MPFFT_ENOMEM;
     return single_stage(P, stage, d_i1, d_i1, d_r, d_ws, ws_bytes, stream, d_pre);
 }
 
@@ -1123,32 +1177,17 @@ struct mpfft_pre {
     size_t bytes;
 };
 
-// the calling thread's device context with its stream, locked by the caller through C->mu
-static int host_ctx(DevCtx **C, int *dev)
-{
-    int ndev = 0;
-    (void)hipGetLastError();
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
-    if (hipGetDevice(dev) != hipSuccess || *dev < 0 || *dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
-    *C = &g_dev[*dev];
-    return MPFFT_OK;
-}
-
 int mpfft_precomp_create(mpfft_pre **out, const uint64_t *i2, long n2, long n1, unsigned long depth, unsigned long w)
 {
     if (!out) return MPFFT_EINVAL;
     *out = nullptr;
     Plan P;
-    int rc = make_plan(&P, n1, n2, depth, w), dev = 0;
+    int rc = make_plan(&P, n1, n2, depth, w);
     if (rc) return rc;
-    DevCtx *Cp;
-    if ((rc = host_ctx(&Cp, &dev))) return rc;
-    DevCtx &C = *Cp;
-    std::lock_guard<std::mutex> lk(C.mu);
-    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
-    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
-    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, (size_t)n2 * 8))) return rc;
-    mpfft_pre *h = new mpfft_pre{dev, n1, n2, depth, w, (int)pw_family(P), nullptr, plan_pre_bytes(P)};
+    HostCall H;
+    if ((rc = H.open(P.bytes, (size_t)n2 * 8))) return rc;
+    DevCtx &C = *H.C;
+    mpfft_pre *h = new mpfft_pre{H.dev, n1, n2, depth, w, (int)pw_family(P), nullptr, plan_pre_bytes(P)};
     if (hipMalloc(&h->d_pre, h->bytes) != hipSuccess) {
         delete h;
         return MPFFT_ENOMEM;
@@ -1170,18 +1209,13 @@ int mpfft_mul_precomp_ex(uint64_t *r, const uint64_t *i1, long n1, const mpfft_p
 {
     if (!pre || n1 != pre->n1) return MPFFT_EINVAL;
     Plan P;
-    int rc = make_plan_pre(&P, n1, pre->n2, pre->depth, pre->w), dev = 0;
+    int rc = make_plan_pre(&P, n1, pre->n2, pre->depth, pre->w);
     if (rc) return rc;
     if ((int)pw_family(P) != pre->family) return MPFFT_EINVAL;   // MPFFT_POINTWISE changed since the cache was made
-    DevCtx *Cp;
-    if ((rc = host_ctx(&Cp, &dev))) return rc;
-    if (dev != pre->dev) return MPFFT_EINVAL;
-    DevCtx &C = *Cp;
-    std::lock_guard<std::mutex> lk(C.mu);
-    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
     const long n2 = pre->n2;
-    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
-    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, (size_t)(2 * n1 + n2) * 8))) return rc;
+    HostCall H;
+    if ((rc = H.open(P.bytes, (size_t)(2 * n1 + n2) * 8, false, pre->dev))) return rc;   // the cache's device only
+    DevCtx &C = *H.C;
     u64 *d_i1 = C.io, *d_r = C.io + n1;
     HIPCHK(hipMemcpyAsync(d_i1, i1, (size_t)n1 * 8, hipMemcpyHostToDevice, C.stream));
     if ((rc = run_all(P, d_r, d_i1, d_i1, C.ws, C.stream, nullptr, (unsigned char *)pre->d_pre))) return rc;
@@ -1208,28 +1242,22 @@ void mpfft_precomp_destroy(mpfft_pre *pre)
 static size_t mod_workspace_bytes(long L, unsigned long depth, unsigned long w, int sqr, bool crt)
 {
     Plan P;
-    if (make_plan_mod(&P, L, depth, w, sqr != 0, crt)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan_mod(&P, L, depth, w, sqr != 0, crt), P);
 }
 
 static int mod_plan_info(long L, unsigned long depth, unsigned long w, long *out, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, false, crt);
-    if (rc) return rc;
-    plan_info_out(P, out);
-    return MPFFT_OK;
+    return plan_info_out(make_plan_mod(&P, L, depth, w, false, crt), P, out);
 }
 
 // out[8], and on the low-word CRT family out[8]: the byte offset of d
 static int mod_workspace_layout(long L, unsigned long depth, unsigned long w, int sqr, size_t *out, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, sqr != 0, crt);
-    if (rc) return rc;
-    layout_out(P, out);
-    if (crt) out[8] = P.off_lowd;
-    return MPFFT_OK;
+    const int rc = layout_out(make_plan_mod(&P, L, depth, w, sqr != 0, crt), P, out);
+    if (!rc && crt) out[8] = P.off_lowd;
+    return rc;
 }
 
 // d_b == d_a on a squaring plan
@@ -1239,9 +1267,8 @@ static int mod_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, l
     Plan P;
     int rc = make_plan_mod(&P, L, depth, w, sqr, crt);
     if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
+    if (!ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
     if (d_r == d_a || d_r == d_b) return MPFFT_EINVAL;
-    (void)hipGetLastError();
     return run_all_mod(P, d_r, d_a, d_b, (unsigned char *)d_ws, (hipStream_t)stream);
 }
 
@@ -1256,8 +1283,7 @@ static int mod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64
     if (stage != MPFFT_STAGE_FWD_COLUMNS && stage != MPFFT_STAGE_SCALE && stage != MPFFT_STAGE_COMBINE
         && stage != MPFFT_STAGE_LOWCONV)
         return single_stage(P, stage, d_a, sqr ? d_a : d_b, d_r, d_ws, ws_bytes, stream);   // the multiply's, Tr = NR
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
+    if (!ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
     if (stage == MPFFT_STAGE_SCALE) return X.unweight();
@@ -1271,9 +1297,7 @@ static int mod_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64
 static int mod_stage_kernels(long L, unsigned long depth, unsigned long w, int sqr, char *buf, size_t len, bool crt)
 {
     Plan P;
-    int rc = make_plan_mod(&P, L, depth, w, sqr != 0, crt);
-    if (rc) return rc;
-    return copy_out(stage_kernel_names(P), buf, len);
+    return stage_names_out(make_plan_mod(&P, L, depth, w, sqr != 0, crt), P, buf, len);
 }
 
 // fully reduced: the top limb 0, or 1 over L zero limbs
@@ -1286,26 +1310,20 @@ static bool mod_reduced(const uint64_t *a, long L)
     return true;
 }
 
-// host operands on the calling thread's device (as mul_host): io holds a, b and r, L + 1 limbs each
-static int mulmod_host(const Plan &P, uint64_t *r, const uint64_t *a, const uint64_t *b)
+// Host operands of a product modulo 2^B + 1 (n = L + 1 limbs each) or 2^B - 1 (n = L) on the calling
+// thread's device, as mul_host: io holds a, b and r; run(d_r, d_a, d_b, ws, stream) is the plan's driver
+template <typename Run>
+static int mod_host(const Plan &P, long n, uint64_t *r, const uint64_t *a, const uint64_t *b, Run run)
 {
-    const long L = P.n1;
-    if (!mod_reduced(a, L) || (!P.sqr && !mod_reduced(b, L))) return MPFFT_EINVAL;
     int rc;
-    (void)hipGetLastError();
-    int ndev = 0, dev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return MPFFT_ENODEV;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MPFFT_MAX_DEV) return MPFFT_ENODEV;
-    DevCtx &C = g_dev[dev];
-    std::lock_guard<std::mutex> lk(C.mu);
-    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
-    const size_t nb = (size_t)(L + 1) * 8;
-    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
-    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, 3 * nb))) return rc;
-    u64 *d_a = C.io, *d_b = P.sqr ? d_a : d_a + (L + 1), *d_r = C.io + 2 * (L + 1);
+    HostCall H;
+    const size_t nb = (size_t)n * 8;
+    if ((rc = H.open(P.bytes, 3 * nb))) return rc;
+    DevCtx &C = *H.C;
+    u64 *d_a = C.io, *d_b = P.sqr ? d_a : d_a + n, *d_r = C.io + 2 * n;
     HIPCHK(hipMemcpyAsync(d_a, a, nb, hipMemcpyHostToDevice, C.stream));
     if (!P.sqr) HIPCHK(hipMemcpyAsync(d_b, b, nb, hipMemcpyHostToDevice, C.stream));
-    if ((rc = run_all_mod(P, d_r, d_a, d_b, C.ws, C.stream))) return rc;
+    if ((rc = run(d_r, d_a, d_b, C.ws, C.stream))) return rc;
     HIPCHK(hipMemcpyAsync(r, d_r, nb, hipMemcpyDeviceToHost, C.stream));
     HIPCHK(hipStreamSynchronize(C.stream));
     g_last_ngpus = 1;
@@ -1318,35 +1336,30 @@ static int mod_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, uns
     Plan P;
     int rc = make_plan_mod(&P, L, depth, w, sqr, crt);
     if (rc) return rc;
-    return mulmod_host(P, r, a, b);
+    if (!mod_reduced(a, L) || (!sqr && !mod_reduced(b, L))) return MPFFT_EINVAL;
+    return mod_host(P, L + 1, r, a, b, [&](u64 *d_r, const u64 *d_a, const u64 *d_b, unsigned char *ws, hipStream_t s) {
+        return run_all_mod(P, d_r, d_a, d_b, ws, s);
+    });
 }
 
-// mpfft_choose's candidates; a candidate's cost is choose_cost at its 2n slots, whatever L (on the
-// low-word CRT family plus the convolution's 4 n^2 multiply-adds).
+// The *_choose and *_next_size of the mod 2^B + 1 families (make_plan_mod, with crt) and of mod 2^B - 1 (cyc:
+// make_plan_cyc): mpfft_choose's candidates; a candidate's cost is choose_cost at its 2n slots, whatever L (on
+// the low-word CRT family plus the convolution's 4 n^2 multiply-adds).
 // fixed_L > 0: the candidates valid for that L; else each candidate at its smallest valid
 // L >= min_L (a multiple of its granularity 2n / 64; crt: at least n limbs, bits1 >= 32)
-static int mulmod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w, bool crt = false)
+static int mod_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w, bool crt, bool cyc = false)
 {
-    double best = -1.0;
-    for (unsigned long d = 2; d <= 24; ++d)
-        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
-            const unsigned long long N = (1ull << d) * wv;
-            if (N % 64) continue;
-            if (N / 64 > 4096) break;
-            const long g = std::max<long>(1, (2L << d) / 64);
-            long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
-            if (crt && fixed_L <= 0) Lc = std::max(Lc, 1L << d);
-            Plan P;
-            if (make_plan_mod(&P, Lc, d, wv, false, crt)) continue;
-            const double c = choose_cost(P);
-            if (best < 0 || c < best) {
-                best = c;
-                *L = Lc;
-                *depth = d;
-                *w = wv;
-            }
-        }
-    if (best < 0) return crt && fixed_L > 0 && fixed_L < 4 ? MPFFT_EINVAL : MPFFT_ETOOBIG;   // L < 4: no bits1 >= 32
+    Plan best;
+    const bool found = search_grid(&best, [&](Plan *p, unsigned long d, unsigned long wv) {
+        const long g = std::max<long>(1, (2L << d) / 64);
+        long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
+        if (crt && fixed_L <= 0) Lc = std::max(Lc, 1L << d);
+        return cyc ? make_plan_cyc(p, Lc, d, wv, CYC_MUL) : make_plan_mod(p, Lc, d, wv, false, crt);
+    });
+    if (!found) return crt && fixed_L > 0 && fixed_L < 4 ? MPFFT_EINVAL : MPFFT_ETOOBIG;   // L < 4: no bits1 >= 32
+    *L = best.n1;
+    *depth = (unsigned long)best.depth;
+    *w = (unsigned long)best.w;
     return MPFFT_OK;
 }
 
@@ -1410,13 +1423,13 @@ int mpfft_mulmod_choose(long L, unsigned long *depth, unsigned long *w)
 {
     long Lc = 0;
     if (L < 1) return MPFFT_EINVAL;
-    return mulmod_pick(L, 0, &Lc, depth, w);
+    return mod_pick(L, 0, &Lc, depth, w, false);
 }
 
 int mpfft_mulmod_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w)
 {
     if (min_L < 1) return MPFFT_EINVAL;
-    return mulmod_pick(0, min_L, L, depth, w);
+    return mod_pick(0, min_L, L, depth, w, false);
 }
 
 // the low-word CRT family (MPFFT_VERSION 7)
@@ -1478,13 +1491,13 @@ int mpfft_mulmodw_choose(long L, unsigned long *depth, unsigned long *w)
 {
     long Lc = 0;
     if (L < 1) return MPFFT_EINVAL;
-    return mulmod_pick(L, 0, &Lc, depth, w, true);
+    return mod_pick(L, 0, &Lc, depth, w, true);
 }
 
 int mpfft_mulmodw_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w)
 {
     if (min_L < 1) return MPFFT_EINVAL;
-    return mulmod_pick(0, min_L, L, depth, w, true);
+    return mod_pick(0, min_L, L, depth, w, true);
 }
 
 // ---- products mod 2^B - 1 (cyc.hpp, make_plan_cyc): run_all on a cyclic plan.  Out of scope as for
@@ -1499,53 +1512,46 @@ int mpfft_mulmodm1_check_params(long L, unsigned long depth, unsigned long w)
 size_t mpfft_mulmodm1_workspace_bytes(long L, unsigned long depth, unsigned long w, int kind)
 {
     Plan P;
-    if (make_plan_cyc(&P, L, depth, w, kind)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan_cyc(&P, L, depth, w, kind), P);
 }
 
 int mpfft_mulmodm1_plan_info(long L, unsigned long depth, unsigned long w, long *out)
 {
     Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
-    if (rc) return rc;
-    plan_info_out(P, out);
-    return MPFFT_OK;
+    return plan_info_out(make_plan_cyc(&P, L, depth, w, CYC_MUL), P, out);
 }
 
 int mpfft_mulmodm1_workspace_layout(long L, unsigned long depth, unsigned long w, int kind, size_t *out)
 {
     Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, kind);
-    if (rc) return rc;
-    layout_out(P, out);
-    return MPFFT_OK;
+    return layout_out(make_plan_cyc(&P, L, depth, w, kind), P, out);
 }
 
 // [p, p + n) and [q, q + m) limbs share an address
 static bool limbs_overlap(const uint64_t *p, long n, const uint64_t *q, long m) { return p < q + m && q < p + n; }
 
+// d_b == d_a on a squaring plan and against the cached operand d_pre (kind CYC_PRE)
+static int cyc_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth, unsigned long w,
+                      int kind, void *d_ws, size_t ws_bytes, void *stream, const void *d_pre = nullptr, size_t pre_bytes = 0)
+{
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, kind);
+    if (rc) return rc;
+    if ((P.pre && !pre_ok(d_pre, pre_bytes, P)) || !ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
+    if (limbs_overlap(d_r, L, d_a, L) || limbs_overlap(d_r, L, d_b, L)) return MPFFT_EINVAL;
+    return run_all(P, d_r, d_a, d_b, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre);
+}
+
 int mpfft_mulmodm1_device(uint64_t *d_r, const uint64_t *d_a, const uint64_t *d_b, long L, unsigned long depth,
                           unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
-    Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (limbs_overlap(d_r, L, d_a, L) || limbs_overlap(d_r, L, d_b, L)) return MPFFT_EINVAL;
-    (void)hipGetLastError();
-    return run_all(P, d_r, d_a, d_b, (unsigned char *)d_ws, (hipStream_t)stream);
+    return cyc_device(d_r, d_a, d_b, L, depth, w, CYC_MUL, d_ws, ws_bytes, stream);
 }
 
 int mpfft_sqrmodm1_device(uint64_t *d_r, const uint64_t *d_a, long L, unsigned long depth, unsigned long w,
                           void *d_ws, size_t ws_bytes, void *stream)
 {
-    Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_SQR);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (limbs_overlap(d_r, L, d_a, L)) return MPFFT_EINVAL;
-    (void)hipGetLastError();
-    return run_all(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream);
+    return cyc_device(d_r, d_a, d_a, L, depth, w, CYC_SQR, d_ws, ws_bytes, stream);
 }
 
 int mpfft_mulmodm1_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long L,
@@ -1558,8 +1564,7 @@ int mpfft_mulmodm1_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, ui
     if ((stage & MPFFT_STAGE_DRIVEN) || stage == MPFFT_STAGE_FOLD_COMBINE) return MPFFT_EINVAL;
     if (stage != MPFFT_STAGE_SCALE && stage != MPFFT_STAGE_COMBINE)   // the multiply's, Tr = NR (the columns split)
         return single_stage(P, stage, d_a, kind == CYC_SQR ? d_a : d_b, d_r, d_ws, ws_bytes, stream);
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
+    if (!ws_ok(d_ws, ws_bytes, P.bytes)) return MPFFT_ENOMEM;
     Exec X(P, (hipStream_t)stream);
     X.single((unsigned char *)d_ws);
     if (stage == MPFFT_STAGE_SCALE) return X.cscale();
@@ -1569,48 +1574,28 @@ int mpfft_mulmodm1_stage(int stage, const uint64_t *d_a, const uint64_t *d_b, ui
 int mpfft_mulmodm1_stage_kernels(long L, unsigned long depth, unsigned long w, int kind, char *buf, size_t len)
 {
     Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, kind);
-    if (rc) return rc;
-    return copy_out(stage_kernel_names(P), buf, len);
+    return stage_names_out(make_plan_cyc(&P, L, depth, w, kind), P, buf, len);
 }
 
-// host operands on the calling thread's device (as mulmod_host): io holds a, b and r, L limbs each
-static int cyc_host(const Plan &P, uint64_t *r, const uint64_t *a, const uint64_t *b)
+// host operands: mod_host with L limbs each and the multiply's driver
+static int cyc_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w, int kind)
 {
-    const long L = P.n1;
-    int rc, dev = 0;
-    DevCtx *Cp;
-    if ((rc = host_ctx(&Cp, &dev))) return rc;
-    DevCtx &C = *Cp;
-    std::lock_guard<std::mutex> lk(C.mu);
-    if (!C.stream) HIPCHK(hipStreamCreateWithFlags(&C.stream, hipStreamNonBlocking));
-    const size_t nb = (size_t)L * 8;
-    if ((rc = ensure_buf((void **)&C.ws, &C.ws_bytes, P.bytes))) return rc;
-    if ((rc = ensure_buf((void **)&C.io, &C.io_bytes, 3 * nb))) return rc;
-    u64 *d_a = C.io, *d_b = P.sqr ? d_a : d_a + L, *d_r = C.io + 2 * L;
-    HIPCHK(hipMemcpyAsync(d_a, a, nb, hipMemcpyHostToDevice, C.stream));
-    if (!P.sqr) HIPCHK(hipMemcpyAsync(d_b, b, nb, hipMemcpyHostToDevice, C.stream));
-    if ((rc = run_all(P, d_r, d_a, d_b, C.ws, C.stream))) return rc;
-    HIPCHK(hipMemcpyAsync(r, d_r, nb, hipMemcpyDeviceToHost, C.stream));
-    HIPCHK(hipStreamSynchronize(C.stream));
-    g_last_ngpus = 1;
-    return MPFFT_OK;
+    Plan P;
+    int rc = make_plan_cyc(&P, L, depth, w, kind);
+    if (rc) return rc;
+    return mod_host(P, L, r, a, b, [&](u64 *d_r, const u64 *d_a, const u64 *d_b, unsigned char *ws, hipStream_t s) {
+        return run_all(P, d_r, d_a, d_b, ws, s);
+    });
 }
 
 int mpfft_mulmodm1_ex(uint64_t *r, const uint64_t *a, const uint64_t *b, long L, unsigned long depth, unsigned long w)
 {
-    Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
-    if (rc) return rc;
-    return cyc_host(P, r, a, b);
+    return cyc_ex(r, a, b, L, depth, w, CYC_MUL);
 }
 
 int mpfft_sqrmodm1_ex(uint64_t *r, const uint64_t *a, long L, unsigned long depth, unsigned long w)
 {
-    Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_SQR);
-    if (rc) return rc;
-    return cyc_host(P, r, a, a);
+    return cyc_ex(r, a, a, L, depth, w, CYC_SQR);
 }
 
 size_t mpfft_mulmodm1_precomp_bytes(long L, unsigned long depth, unsigned long w)
@@ -1624,62 +1609,27 @@ int mpfft_mulmodm1_precomp_device(void *d_pre, size_t pre_bytes, const uint64_t 
                                   unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_MUL);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_all(P, nullptr, nullptr, d_b, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre, true);
+    return device_run(make_plan_cyc(&P, L, depth, w, CYC_MUL), P, nullptr, nullptr, d_b, d_ws, ws_bytes, stream, d_pre,
+                      pre_bytes, true);
 }
 
 int mpfft_mulmodm1_mul_precomp_device(uint64_t *d_r, const uint64_t *d_a, const void *d_pre, size_t pre_bytes, long L,
                                       unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
-    Plan P;
-    int rc = make_plan_cyc(&P, L, depth, w, CYC_PRE);
-    if (rc) return rc;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    if (!d_pre || pre_bytes < plan_pre_bytes(P)) return MPFFT_ENOMEM;
-    if (limbs_overlap(d_r, L, d_a, L)) return MPFFT_EINVAL;
-    (void)hipGetLastError();
-    return run_all(P, d_r, d_a, d_a, (unsigned char *)d_ws, (hipStream_t)stream, nullptr, (unsigned char *)d_pre);
-}
-
-// as mulmod_pick, on the cyclic plans
-static int cyc_pick(long fixed_L, long min_L, long *L, unsigned long *depth, unsigned long *w)
-{
-    double best = -1.0;
-    for (unsigned long d = 2; d <= 24; ++d)
-        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
-            const unsigned long long N = (1ull << d) * wv;
-            if (N % 64) continue;
-            if (N / 64 > 4096) break;
-            const long g = std::max<long>(1, (2L << d) / 64);
-            const long Lc = fixed_L > 0 ? fixed_L : (min_L + g - 1) / g * g;
-            Plan P;
-            if (make_plan_cyc(&P, Lc, d, wv, CYC_MUL)) continue;
-            const double c = choose_cost(P);
-            if (best < 0 || c < best) {
-                best = c;
-                *L = Lc;
-                *depth = d;
-                *w = wv;
-            }
-        }
-    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+    return cyc_device(d_r, d_a, d_a, L, depth, w, CYC_PRE, d_ws, ws_bytes, stream, d_pre, pre_bytes);
 }
 
 int mpfft_mulmodm1_choose(long L, unsigned long *depth, unsigned long *w)
 {
     long Lc = 0;
     if (L < 1) return MPFFT_EINVAL;
-    return cyc_pick(L, 0, &Lc, depth, w);
+    return mod_pick(L, 0, &Lc, depth, w, false, true);
 }
 
 int mpfft_mulmodm1_next_size(long min_L, long *L, unsigned long *depth, unsigned long *w)
 {
     if (min_L < 1) return MPFFT_EINVAL;
-    return cyc_pick(0, min_L, L, depth, w);
+    return mod_pick(0, min_L, L, depth, w, false, true);
 }
 
 // ---- sums of products (mpfft_dot_*, MPFFT_VERSION 8) -----------------------------------------
@@ -1692,64 +1642,54 @@ int mpfft_dot_check_params(long K, long n1, long n2, unsigned long depth, unsign
 int mpfft_dot_plan_info(long K, long n1, long n2, unsigned long depth, unsigned long w, long *out)
 {
     Plan P;
-    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
-    if (rc) return rc;
-    plan_info_out(P, out);
-    return MPFFT_OK;
+    return plan_info_out(make_plan_dot(&P, K, n1, n2, depth, w), P, out);
 }
 
 size_t mpfft_dot_workspace_bytes(long K, long n1, long n2, unsigned long depth, unsigned long w)
 {
     Plan P;
-    if (make_plan_dot(&P, K, n1, n2, depth, w)) return 0;
-    return P.bytes;
+    return bytes_or_0(make_plan_dot(&P, K, n1, n2, depth, w), P);
+}
+
+// out[11]: the multiply's eight words, then C's arrays
+static int dot_layout_out(int rc, const Plan &P, size_t *out)
+{
+    if ((rc = layout_out(rc, P, out))) return rc;
+    out[8] = P.off_digC; out[9] = P.off_topC; out[10] = P.off_cbC;
+    return MPFFT_OK;
 }
 
 int mpfft_dot_workspace_layout(long K, long n1, long n2, unsigned long depth, unsigned long w, size_t *out)
 {
     Plan P;
-    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
-    if (rc) return rc;
-    layout_out(P, out);
-    out[8] = P.off_digC; out[9] = P.off_topC; out[10] = P.off_cbC;
-    return MPFFT_OK;
+    return dot_layout_out(make_plan_dot(&P, K, n1, n2, depth, w), P, out);
 }
 
 int mpfft_dot_choose(long K, long n1, long n2, unsigned long *depth, unsigned long *w)
 {
     if (K < 1 || K > DOT_MAX) return MPFFT_EINVAL;
-    double best = -1.0;
-    for (unsigned long d = 2; d <= 24; ++d)
-        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
-            const unsigned long long N = (1ull << d) * wv;
-            if (N % 64) continue;
-            if (N / 64 > 4096) break;
-            Plan P;
-            if (make_plan_dot(&P, K, n1, n2, d, wv)) continue;
-            const double c = choose_cost(P);
-            if (best < 0 || c < best) {
-                best = c;
-                *depth = d;
-                *w = wv;
-            }
-        }
-    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+    return choose_on_grid(depth, w, [&](Plan *p, unsigned long d, unsigned long wv) { return make_plan_dot(p, K, n1, n2, d, wv); });
+}
+
+// The device entry of the sums: signed (sd: the workspace is sd_layout's) and not (neg = 0, the dot plan's own)
+static int dot_device(int rc, const Plan &P, bool sd, uint64_t *d_r, long K, u64 neg, const uint64_t *const *d_a,
+                      const uint64_t *const *d_b, void *d_ws, size_t ws_bytes, void *stream)
+{
+    if (rc) return rc;
+    if (!d_r || !d_a || !d_b) return MPFFT_EINVAL;
+    if (!ws_ok(d_ws, ws_bytes, sd ? sd_layout(P).bytes : P.bytes)) return MPFFT_ENOMEM;
+    return run_dot(P, K, d_r, (unsigned char *)d_ws, (hipStream_t)stream, [&](long i, const u64 **a, const u64 **b) {
+        *a = d_a[i];
+        *b = d_b[i];
+        return *a && *b ? MPFFT_OK : MPFFT_EINVAL;
+    }, neg);
 }
 
 int mpfft_dot_device(uint64_t *d_r, long K, const uint64_t *const *d_a, const uint64_t *const *d_b, long n1, long n2,
                      unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
-    if (rc) return rc;
-    if (!d_r || !d_a || !d_b) return MPFFT_EINVAL;
-    if (!d_ws || ws_bytes < P.bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_dot(P, K, d_r, (unsigned char *)d_ws, (hipStream_t)stream, [&](long i, const u64 **a, const u64 **b) {
-        *a = d_a[i];
-        *b = d_b[i];
-        return *a && *b ? MPFFT_OK : MPFFT_EINVAL;
-    });
+    return dot_device(make_plan_dot(&P, K, n1, n2, depth, w), P, false, d_r, K, 0, d_a, d_b, d_ws, ws_bytes, stream);
 }
 
 // The pointwise field of a dot plan: what the first term runs + what the later terms run
@@ -1801,23 +1741,17 @@ int mpfft_dot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b,
 // term's copies are queued on the context's stream in front of its forward passes.
 // neg: mpfft_sdot_ex's sign mask (the workspace then has sd_layout's regions behind the dot's; D lives
 // there, so no operand is kept after its term)
-static int dot_host(uint64_t *r, long K, u64 neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
-                    unsigned long depth, unsigned long w)
+// rc, P: the caller's make_plan_dot or make_plan_sdot
+static int dot_host(int rc, const Plan &P, uint64_t *r, long K, u64 neg, const uint64_t *const *a, const uint64_t *const *b)
 {
-    Plan P;
-    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
     if (rc) return rc;
     if (!r || !a || !b) return MPFFT_EINVAL;
-    DevCtx *C;
-    int dev = 0;
-    if ((rc = host_ctx(&C, &dev))) return rc;
-    std::lock_guard<std::mutex> lk(C->mu);
-    if (!C->stream) HIPCHK(hipStreamCreateWithFlags(&C->stream, hipStreamNonBlocking));
-    if ((rc = ensure_buf((void **)&C->ws, &C->ws_bytes, neg ? sd_layout(P).bytes : P.bytes))) return rc;
-    if ((rc = ensure_buf((void **)&C->io, &C->io_bytes, (size_t)(n1 + n2 + P.total) * 8))) return rc;
-    u64 *d_a = C->io, *d_b = d_a + n1, *d_r = d_b + n2;
-    hipStream_t s = C->stream;
-    rc = run_dot(P, K, d_r, C->ws, s, [&](long i, const u64 **pa, const u64 **pb) {
+    const long n1 = P.n1, n2 = P.n2;
+    HostCall H;
+    if ((rc = H.open(neg ? sd_layout(P).bytes : P.bytes, (size_t)(n1 + n2 + P.total) * 8))) return rc;
+    u64 *d_a = H.C->io, *d_b = d_a + n1, *d_r = d_b + n2;
+    hipStream_t s = H.C->stream;
+    rc = run_dot(P, K, d_r, H.C->ws, s, [&](long i, const u64 **pa, const u64 **pb) {
         if (!a[i] || !b[i]) return (int)MPFFT_EINVAL;
         HIPCHK(hipMemcpyAsync(d_a, a[i], (size_t)n1 * 8, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(d_b, b[i], (size_t)n2 * 8, hipMemcpyHostToDevice, s));
@@ -1837,7 +1771,8 @@ static int dot_host(uint64_t *r, long K, u64 neg, const uint64_t *const *a, cons
 int mpfft_dot_ex(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
                  unsigned long depth, unsigned long w)
 {
-    return dot_host(r, K, 0, a, b, n1, n2, depth, w);
+    Plan P;
+    return dot_host(make_plan_dot(&P, K, n1, n2, depth, w), P, r, K, 0, a, b);
 }
 
 int mpfft_dot_auto(uint64_t *r, long K, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2)
@@ -1873,9 +1808,8 @@ size_t mpfft_sdot_workspace_bytes(long K, long n1, long n2, unsigned long depth,
 int mpfft_sdot_workspace_layout(long K, long n1, long n2, unsigned long depth, unsigned long w, size_t *out)
 {
     Plan P;
-    int rc = make_plan_dot(&P, K, n1, n2, depth, w);
+    const int rc = dot_layout_out(make_plan_dot(&P, K, n1, n2, depth, w), P, out);
     if (rc) return rc;
-    if ((rc = mpfft_dot_workspace_layout(K, n1, n2, depth, w, out))) return rc;
     const SdLayout L = sd_layout(P);
     out[11] = L.off_scr;
     out[12] = L.off_d;
@@ -1886,25 +1820,14 @@ int mpfft_sdot_device(uint64_t *d_r, long K, uint64_t neg, const uint64_t *const
                       long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
 {
     Plan P;
-    int rc = make_plan_sdot(&P, K, neg, n1, n2, depth, w);
-    if (rc) return rc;
-    if (!d_r || !d_a || !d_b) return MPFFT_EINVAL;
-    if (!d_ws || ws_bytes < sd_layout(P).bytes) return MPFFT_ENOMEM;
-    (void)hipGetLastError();
-    return run_dot(P, K, d_r, (unsigned char *)d_ws, (hipStream_t)stream, [&](long i, const u64 **a, const u64 **b) {
-        *a = d_a[i];
-        *b = d_b[i];
-        return *a && *b ? MPFFT_OK : MPFFT_EINVAL;
-    }, neg);
+    return dot_device(make_plan_sdot(&P, K, neg, n1, n2, depth, w), P, true, d_r, K, neg, d_a, d_b, d_ws, ws_bytes, stream);
 }
 
 int mpfft_sdot_ex(uint64_t *r, long K, uint64_t neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2,
                   unsigned long depth, unsigned long w)
 {
     Plan P;
-    const int rc = make_plan_sdot(&P, K, neg, n1, n2, depth, w);
-    if (rc) return rc;
-    return dot_host(r, K, neg, a, b, n1, n2, depth, w);
+    return dot_host(make_plan_sdot(&P, K, neg, n1, n2, depth, w), P, r, K, neg, a, b);
 }
 
 int mpfft_sdot_auto(uint64_t *r, long K, uint64_t neg, const uint64_t *const *a, const uint64_t *const *b, long n1, long n2)
@@ -1965,25 +1888,9 @@ int mpfft_release(void)
     return MPFFT_OK;
 }
 
-
 int mpfft_choose(long n1, long n2, unsigned long *depth, unsigned long *w)
 {
-    double best = -1.0;
-    for (unsigned long d = 2; d <= 24; ++d)
-        for (unsigned long wv = 1; wv <= 4096; wv *= 2) {
-            const unsigned long long N = (1ull << d) * wv;
-            if (N % 64) continue;
-            if (N / 64 > 4096) break;
-            Plan P;
-            if (make_plan(&P, n1, n2, d, wv)) continue;
-            const double c = choose_cost(P);
-            if (best < 0 || c < best) {
-                best = c;
-                *depth = d;
-                *w = wv;
-            }
-        }
-    return best < 0 ? MPFFT_ETOOBIG : MPFFT_OK;
+    return choose_on_grid(depth, w, [&](Plan *p, unsigned long d, unsigned long wv) { return make_plan(p, n1, n2, d, wv); });
 }
 
 int mpfft_mul_auto(uint64_t *r1, const uint64_t *i1, long n1, const uint64_t *i2, long n2)
