@@ -29,7 +29,7 @@ typedef long mp_size_t;
 typedef unsigned long mp_bitcnt_t;
 #endif
 
-#define MPFFT_VERSION 9
+#define MPFFT_VERSION 10
 
 #define MPFFT_OK 0
 #define MPFFT_EINVAL 1          /* n1, n2 < 1; depth outside [2, 30]; n*w not a multiple of 64 */
@@ -69,8 +69,8 @@ int mpfft_release(void);
  * `stream` (a hipStream_t, NULL = default) and not synchronised.  d_ws must hold
  * mpfft_workspace_bytes(n1, n2, depth, w) bytes.
  * Alignment, for this entry and for the mpfft_sqr_, mpfft_mulmod_, mpfft_mulmodw_, mpfft_mulmodm1_,
- * mpfft_precomp_ / mpfft_mul_precomp_, mpfft_dot_ and mpfft_sdot_ device and stage entries below:
- * operands and results (d_r, d_i1, d_i2, d_a, d_b and the pointers in a term array) need limb
+ * mpfft_precomp_ / mpfft_mul_precomp_, mpfft_dot_, mpfft_sdot_ and mpfft_matmul_ device and stage entries
+ * below: operands and results (d_r, d_i1, d_i2, d_a, d_b and the pointers in a term, entry or result array) need limb
  * (8-byte) alignment only, so rp + k is a valid argument as it is for the mpn_* calls these
  * replace (tests/test_gpu_limb_aligned.py).  mpfft_mul6_device, the mpfft_shard_* entries and
  * mpfft_mul_multi_device read their operands limb by limb as well, but no test runs them on such
@@ -348,9 +348,9 @@ int mpfft_mulmodw_next_size(long min_L, long *L, unsigned long *depth, unsigned 
  * Under mpfft_profile_begin/end every term claims a call slot (max_calls >= K per sum): the
  * forward and pointwise stage times are sums over the terms, the returned call count counts terms.
  * Signed terms (a b - c d) are the mpfft_sdot_* entries below.
- * Not covered: accumulating in the inner transform domain (one inner
- * inverse for all terms), cached or shared forward transforms between terms (a 2x2 matrix
- * product with eight forward transforms), squares as terms (a_i == b_i runs as a product), the
+ * Matrix products with shared forward transforms and one inner inverse per result entry are the
+ * mpfft_matmul_* entries below.
+ * Not covered: squares as terms (a_i == b_i runs as a product), the
  * sqrt2 front end, the mod 2^B +- 1 families, the sharded / multi-GPU entries and
  * mpfft_set_devices routing. */
 #define MPFFT_DOT_MAX 64
@@ -440,6 +440,77 @@ int mpfft_sdot_stage_kernels(long K, uint64_t neg, long n1, long n2, unsigned lo
 #define MPFFT_STAGE_SD_FIX 11   /* d_r <- d_r + D - (D << 64 n1), n1 + n2 + 1 limbs */
 int mpfft_sdot_stage(int stage, long K, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1, long n2,
                      unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+
+/* ---- small matrix products (MPFFT_VERSION 10): R = X Y, R[i][j] = sum_{t < k} X[i][t] Y[t][j], X m x k with
+ * entries of n1 limbs, Y k x p with entries of n2 limbs, R m x p with entries of n1 + n2 + 1 limbs (the top
+ * one below k), 1 <= m, k, p <= MPFFT_MM_MAX, exact, single device, with new_mpn_mul's meaning of
+ * (depth, w) -- the 2x2 by 2x2 and 2x2 by 2x1 products of binary splitting, half-GCD steps and
+ * determinants, which as m p calls of mpfft_dot_device transform every operand p (or m) times.
+ * Plan, (depth, w) validity, operand bound and chooser are mpfft_dot_*'s at K = k: use
+ * mpfft_dot_choose(k, n1, n2), mpfft_dot_plan_info and the bindings' dot_max_limbs.  Every R[i][j] is
+ * limb-equal to mpfft_dot_device on the same k terms; (1, k, 1) is the dot, (1, 1, 1) the multiply with a
+ * zero top limb.  Operands are only read; pointers may repeat anywhere in X and Y, X[i][t] == Y[t][j]
+ * included when n1 == n2; no result overlaps an operand or another result.  Matrices are row-major arrays
+ * of pointers.
+ * Forward side, once per matrix entry (m k + k p single-operand forward transforms): split, forward
+ * columns and rows, then the entry's transformed slots go to a cache region in the workspace, in
+ * mpfft_precomp_*'s layout -- on nested plans k_pwsx records, the slots after the inner forward transform,
+ * the row levels the plan fuses paid there once.  Per result entry: on nested plans k_pwmm multiplies the
+ * k pairs of records of a slot, adds the products with their signs in the inner ring (the pending
+ * exponents of a record depend on the thread alone, so no product is rotated) and runs one inner
+ * inverse and one output stage; the other families copy X's cached slots into a staging array, run the
+ * multiply's pointwise in place with B read from Y's cache and add with k_slotacc (a correctness path,
+ * not tuned).  The multiply's inverse rows, truncated inverse columns, scaling and combine then run once
+ * per result entry, each combine clearing its own look-back flags and ticket counter.  A fixed number
+ * of launches per product, no host synchronisation.
+ * Status: MPFFT_EINVAL for m, k or p outside [1, MPFFT_MM_MAX] (and null pointers), MPFFT_ENOMEM for a
+ * workspace that is too small, the rest as mpfft_dot_check_params(k, ...).
+ * Workspace: the dot workspace at K = k (A's and B's arrays stage an X and a Y operand's forward
+ * transform, C holds one result entry's sum), then m k + k p cache regions at a uniform stride, X's
+ * entries row-major first; every offset 256-byte aligned.  Its size depends on the shape alone, it need
+ * not be cleared, and a dot workspace laid at its front is valid for mpfft_dot_stage.
+ * Under mpfft_profile_begin/end a product claims m k + k p + m p call slots: one per matrix entry, whose
+ * forward-columns and forward-rows stages are that operand's and whose pointwise stage is its cache
+ * store (the later stages empty), then one per result entry, whose forward stages are empty, whose
+ * pointwise stage is the sum over its k terms and whose later stages are its inverse side.  The stage
+ * times returned are the product's, the call count m k + k p + m p.
+ * Not covered: signed entries, a persistent matrix handle applied to many vectors (the caches live in
+ * the workspace and are rewritten by every call), squares as terms, the mod 2^B +- 1 families, the sqrt2
+ * front end, the sharded / multi-GPU entries and mpfft_set_devices routing. */
+#define MPFFT_MM_MAX 4
+int mpfft_matmul_check_params(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w);
+size_t mpfft_matmul_workspace_bytes(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w);   /* 0 on invalid parameters */
+/* out[14]: the eleven entries of mpfft_dot_workspace_layout(k, ...), then the byte offset of cache 0, the
+ * stride between caches in bytes and their number m k + k p (X[i][t] is cache i k + t, Y[t][j] cache
+ * m k + t p + j). */
+int mpfft_matmul_workspace_layout(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w, size_t *out);
+/* d_r: host array of m p device pointers, d_a of m k, d_b of k p, row-major (read during the call only).
+ * Queued on `stream`, not synchronised. */
+int mpfft_matmul_device(uint64_t *const *d_r, long m, long k, long p, const uint64_t *const *d_a, const uint64_t *const *d_b,
+                        long n1, long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream);
+/* Host pointers: the operands go through the device context's io buffer one at a time.
+ * mpfft_matmul_auto: (depth, w) from mpfft_dot_choose(k, n1, n2). */
+int mpfft_matmul_ex(uint64_t *const *r, long m, long k, long p, const uint64_t *const *a, const uint64_t *const *b, long n1,
+                    long n2, unsigned long depth, unsigned long w);
+int mpfft_matmul_auto(uint64_t *const *r, long m, long k, long p, const uint64_t *const *a, const uint64_t *const *b, long n1,
+                      long n2);
+/* mpfft_dot_stage_kernels' seven fields; the pointwise field reads "k_pwsx<M>... + k_pwmm<M> (single launch,
+ * K=...)" on nested plans (one launch for a result entry's k terms: it measured faster than k launches of one
+ * term each at every M), "<kernel> (B cached) + k_slotacc" elsewhere. */
+int mpfft_matmul_stage_kernels(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w, char *buf,
+                               size_t len);
+/* (tests) The two stages of this family on its workspace; every other stage is forwarded to
+ * mpfft_dot_stage(stage, k, ...) on the dot workspace at the front (kk, ea, eb unused).  Like
+ * mpfft_dot_stage it never fuses row levels.  MPFFT_STAGE_MM_STORE: the row arrays of operand 0 (A's
+ * arrays, for a cache of X: ea[0] < m k) or operand 1 (B's) -> cache ea[0].  MPFFT_STAGE_MM_POINTWISE:
+ * C <- sum_{i < kk} cache ea[i] * cache eb[i] over the live slots, 1 <= kk <= MPFFT_MM_MAX, any cache
+ * indices; or-ed with MPFFT_STAGE_ACC: C <- C + that sum.  On the families that multiply in place A's
+ * arrays are overwritten. */
+#define MPFFT_STAGE_MM_STORE 12
+#define MPFFT_STAGE_MM_POINTWISE 13
+int mpfft_matmul_stage(int stage, long m, long k, long p, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1,
+                       long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream, long kk,
+                       const int *ea, const int *eb);
 
 /* ---- sqrt2 front end: replaces new_mpn_mul6, mul_fft.c:3573-3668 ----------------------
  * A length-4n convolution mod 2^N + 1 (N = 2^depth w) through the 4n-th root of unity

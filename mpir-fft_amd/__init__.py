@@ -70,6 +70,7 @@ _ip, _lp, _ulp, _szp, _pp = (ctypes.POINTER(t) for t in (_I, _L, _UL, _SZ, _vp))
 _MUL = [_L, _L, _UL, _UL]    # (n1, n2, depth, w)
 _MOD = [_L, _UL, _UL]        # (L, depth, w), and a square's (n, depth, w)
 _DOT = [_L] + _MUL           # (K, n1, n2, depth, w)
+_MM = [_L, _L, _L] + _MUL    # (m, k, p, n1, n2, depth, w)
 _WS = [_vp, _SZ, _vp]        # (d_ws, ws_bytes, stream)
 _TEXT = [_cp, _SZ]           # (buf, len)
 
@@ -145,6 +146,13 @@ def _signatures():
         ("mpfft_sdot_ex", _I, [_u64p, _L, _U64, _pp, _pp] + _MUL), ("mpfft_sdot_auto", _I, [_u64p, _L, _U64, _pp, _pp, _L, _L]),
         ("mpfft_sdot_stage_kernels", _I, [_L, _U64] + _MUL + _TEXT),
         ("mpfft_sdot_stage", _I, [_I, _L, _vp, _vp, _vp] + _MUL + _WS),
+        # 10: small matrix products
+        ("mpfft_matmul_check_params", _I, _MM), ("mpfft_matmul_workspace_bytes", _SZ, _MM),
+        ("mpfft_matmul_workspace_layout", _I, _MM + [_szp]),
+        ("mpfft_matmul_device", _I, [_pp, _L, _L, _L, _pp, _pp] + _MUL + _WS),
+        ("mpfft_matmul_ex", _I, [_pp, _L, _L, _L, _pp, _pp] + _MUL), ("mpfft_matmul_auto", _I, [_pp, _L, _L, _L, _pp, _pp, _L, _L]),
+        ("mpfft_matmul_stage_kernels", _I, _MM + _TEXT),
+        ("mpfft_matmul_stage", _I, [_I, _L, _L, _L, _vp, _vp, _vp] + _MUL + _WS + [_L, _ip, _ip]),
         # 4, 7, 6: mod 2^B + 1, with the low-word CRT, mod 2^B - 1
     ] + _mod_signatures("mulmod", "sqrmod") + _mod_signatures("mulmodw", "sqrmodw") + _mod_signatures("mulmodm1", "sqrmodm1")
 

@@ -640,20 +640,72 @@ struct Exec {
 
     // operand B's live slots in the row arrays -> the cache (pre_make): k_pwsx on nested plans (the
     // row levels the plan fuses run in its loaders), else a copy of the limbs and carry limbs
-    int precomp_store()
+    // op: the operand whose row arrays are stored (the matrix products cache operand 0's as well)
+    int precomp_store(int op = 1)
     {
         const long cnt = (long)rcount * P.NC;
         if (!pre) return MPFFT_EINVAL;
         if (!pwss_active()) {
-            HIPCHK(hipMemcpyAsync(pre, row.dig[1], plan_pre_dig_bytes(P), hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(pre + plan_pre_dig_bytes(P), row.top[1], (size_t)cnt * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(pre, row.dig[op], plan_pre_dig_bytes(P), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(pre + plan_pre_dig_bytes(P), row.top[op], (size_t)cnt * 4, hipMemcpyDeviceToDevice, s));
             return MPFFT_OK;
         }
         const int lk = pwss_lk_of(P.l), M = pw_inner_limbs(P.l, lk), fz = row_fused();
         pw_pre_fn f = pw_get_pre(M, lk, fz);
         if (!f) return MPFFT_EUNSUPPORTED;
-        return launch(f, dim3((unsigned)cnt), dim3(1u << lk), pw_lds(M, 1 << lk, (int)P.l), (const u64 *)row.dig[1],
-                      (const u64 *)row.cb[1], (const int *)row.top[1], (int)P.l, pre, (unsigned long long *)nullptr);
+        return launch(f, dim3((unsigned)cnt), dim3(1u << lk), pw_lds(M, 1 << lk, (int)P.l), (const u64 *)row.dig[op],
+                      (const u64 *)row.cb[op], (const int *)row.top[op], (int)P.l, pre, (unsigned long long *)nullptr);
+    }
+
+    // ---- small matrix products (mm_layout): one result entry's pointwise sum -------------------
+    // C <- (acc: C +) sum_{i < kk} cache ea[i] * cache eb[i] over the live slots; caches: region e at
+    // caches + e stride.  Nested plans: k_pwmm on the records.  Elsewhere the caches hold transformed
+    // row arrays: per term a copy of cache ea[i] into the staging array (the first term of a fresh
+    // sum: into C itself), the plan's pointwise in place with B read from cache eb[i], and k_slotacc
+    // for every term but that first.  The views are left as they were.
+    int pointwise_mm(const unsigned char *caches, size_t stride, int kk, const int *ea, const int *eb, bool acc)
+    {
+        const long cnt = (long)rcount * P.NC;
+        if (cnt == 0 || !cview.dig[0] || !caches || kk < 1 || kk > MM_MAX) return MPFFT_EINVAL;
+        if (pwss_active()) {
+            const int lk = pwss_lk_of(P.l), M = pw_inner_limbs(P.l, lk);
+            const size_t lds = pw_lds(M, 1 << lk, (int)P.l);
+            const dim3 grid((unsigned)cnt), block(1u << lk);
+            // one launch for all kk terms: the sum in the inner ring, one inner inverse (against kk launches of
+            // one term each, accumulating in C: 0.73 of their time at M = 18)
+            pw_mm_fn f = pw_get_mm(M, lk, acc);
+            if (!f) return MPFFT_EUNSUPPORTED;   // a missing instance is an error
+            unsigned pa = 0, pb = 0;
+            for (int i = 0; i < kk; ++i) {
+                pa |= (unsigned)ea[i] << (8 * i);
+                pb |= (unsigned)eb[i] << (8 * i);
+            }
+            return launch(f, grid, block, lds, caches, (unsigned long long)stride, kk, pa, pb, (int)P.l, cview.dig[0],
+                          cview.cb[0], cview.top[0]);
+        }
+        const View row0 = row, col0 = col;
+        const unsigned char *pre0 = pre;
+        int rc = MPFFT_OK;
+        for (int i = 0; i < kk && !rc; ++i) {
+            const bool first = i == 0 && !acc;
+            row = row0;
+            col = col0;
+            if (first) view_op0(cview);
+            const unsigned char *xa = caches + (size_t)ea[i] * stride;
+            pre = (unsigned char *)(caches + (size_t)eb[i] * stride);
+            row.dig[1] = (u64 *)pre;
+            row.top[1] = (int *)(pre + plan_pre_dig_bytes(P));
+            // the cached operand is canonical: its limbs, its carry limbs, no carry masks
+            HIPCHK(hipMemcpyAsync(row.dig[0], xa, plan_pre_dig_bytes(P), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(row.top[0], xa + plan_pre_dig_bytes(P), (size_t)cnt * 4, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemsetAsync(row.cb[0], 0, (size_t)cnt * cb_words((int)P.l) * 8, s));
+            rc = pointwise();
+            if (!rc && !first) rc = slot_acc(cnt);
+        }
+        row = row0;
+        col = col0;
+        pre = (unsigned char *)pre0;
+        return rc;
     }
 
     int pointwise()

@@ -365,6 +365,82 @@ static int run_dot(const Plan &P, long K, u64 *d_r, unsigned char *ws, hipStream
     return rc;
 }
 
+// The small matrix product R = X Y (mpfft_matmul_*; X m x k, Y k x p) on the dot plan at K = k and
+// mm_layout's workspace.  Forward side, once per matrix entry: split, forward columns and forward rows
+// of that operand alone -- X's entries as operand 0 in A's arrays, Y's as operand 1 in B's, each under
+// its own zero-row bound -- then Exec::precomp_store into the entry's cache region (k_pwsx on nested
+// plans, with the row levels the plan fuses).  Then per result entry: Exec::pointwise_mm writes C, and
+// the multiply's inverse rows, truncated inverse columns, scaling and combine run on C into d_r[i p + j].
+// What the inverse side of one entry assumes, and how each entry gets it:
+//   * the combine's look-back flags and ticket counter are zero: no forward pass clears them here
+//     (Exec::zflags stays null), so every combine clears its own in front of its launch;
+//   * C's live slots hold this entry's pointwise sum: k_pwmm (or the first term's in-place product)
+//     overwrites every live slot's limbs, carry masks and carry limb, nothing of the previous entry's
+//     inverse is read;
+//   * rows [Tr, NR) of C: the truncated inverse writes a row there (FILL) before it reads it;
+//   * the deferred doubling's rows (dbl_lo, dbl_hi), the pending FILL and the chain are set by itft
+//     itself on every call; the fold's meta words are written by k_cmeta in front of every combine;
+//   * the row and column views point at C.
+// opnd(e, &d): the device operand of matrix entry e (X's m k entries row-major, then Y's k p); the host
+// entries queue its copy there.
+// Profiling: every matrix entry claims a call slot and marks its forward columns and rows; its cache
+// store counts as that slot's pointwise stage and the later boundaries are marked at once.  Every result
+// entry claims a slot whose forward stages are empty and which carries the pointwise sum and the
+// inverse side.  A product claims m k + k p + m p slots.
+template <typename Opnd>
+static int run_matmul(const Plan &P, int m, int k, int p, u64 *const *d_r, unsigned char *ws, hipStream_t s, Opnd opnd)
+{
+    static_assert(MM_MAX == MPFFT_MM_MAX, "one bound on the matrix dimensions");
+    const MmLayout L = mm_layout(P, m, k, p);
+    Exec X(P, s);
+    X.single(ws);
+    X.drive_single();
+    X.fuse_row_last = true;
+    X.pre_make = true;
+    const View ab = X.col;
+    int rc = MPFFT_OK;
+    for (int e = 0; e < L.ncache; ++e) {
+        const int op = e < m * k ? 0 : 1;
+        const long n = op ? P.n2 : P.n1;
+        const u64 *d = nullptr;
+        ProfCall pc;
+        pc.mark(0, s);
+        if ((rc = opnd(e, &d))) return rc;
+        X.pre = ws + L.off_cache + (size_t)e * L.stride;
+        if ((rc = X.fwd_columns(d, n, d, n, 1, op))) return rc;
+        pc.mark(1, s);
+        if ((rc = X.fwd_rows(1, op))) return rc;
+        pc.mark(2, s);
+        if ((rc = X.precomp_store(op))) return rc;
+        for (int st = 3; st <= MPFFT_NSTAGES; ++st) pc.mark(st, s);
+    }
+    for (int i = 0; i < m; ++i)
+        for (int j = 0; j < p; ++j) {
+            int ea[MM_MAX], eb[MM_MAX];
+            for (int t = 0; t < k; ++t) {
+                ea[t] = i * k + t;
+                eb[t] = m * k + t * p + j;
+            }
+            ProfCall pc;
+            for (int st = 0; st <= 2; ++st) pc.mark(st, s);
+            X.col = X.row = ab;
+            if ((rc = X.pointwise_mm(ws + L.off_cache, L.stride, k, ea, eb, false))) return rc;
+            pc.mark(3, s);
+            X.view_op0(X.cview);
+            if ((rc = X.inv_rows())) return rc;
+            pc.mark(4, s);
+            if ((rc = X.itft(0, P.NR, P.Tr))) return rc;
+            pc.mark(5, s);
+            if ((rc = X.scale())) return rc;
+            pc.mark(6, s);
+            u64 *r = d_r[i * p + j];
+            rc = X.fold ? X.combine_fold(r, ws, X.dbl_lo, X.dbl_hi) : X.combine_single(r, ws);
+            pc.mark(7, s);
+            if (rc) return rc;
+        }
+    return rc;
+}
+
 // ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
@@ -1781,6 +1857,156 @@ int mpfft_dot_auto(uint64_t *r, long K, const uint64_t *const *a, const uint64_t
     const int rc = mpfft_dot_choose(K, n1, n2, &d, &wv);
     if (rc) return rc;
     return mpfft_dot_ex(r, K, a, b, n1, n2, d, wv);
+}
+
+// ---- small matrix products (mpfft_matmul_*, MPFFT_VERSION 10) -----------------------------------
+int mpfft_matmul_check_params(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    return make_plan_matmul(&P, m, k, p, n1, n2, depth, w);
+}
+
+size_t mpfft_matmul_workspace_bytes(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    if (make_plan_matmul(&P, m, k, p, n1, n2, depth, w)) return 0;
+    return mm_layout(P, m, k, p).bytes;
+}
+
+int mpfft_matmul_workspace_layout(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w, size_t *out)
+{
+    Plan P;
+    int rc = make_plan_matmul(&P, m, k, p, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!out) return MPFFT_EINVAL;
+    if ((rc = dot_layout_out(rc, P, out))) return rc;
+    const MmLayout L = mm_layout(P, m, k, p);
+    out[11] = L.off_cache; out[12] = L.stride; out[13] = (size_t)L.ncache;
+    return MPFFT_OK;
+}
+
+int mpfft_matmul_device(uint64_t *const *d_r, long m, long k, long p, const uint64_t *const *d_a, const uint64_t *const *d_b,
+                        long n1, long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream)
+{
+    Plan P;
+    int rc = make_plan_matmul(&P, m, k, p, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!d_r || !d_a || !d_b) return MPFFT_EINVAL;
+    for (long e = 0; e < m * p; ++e)
+        if (!d_r[e]) return MPFFT_EINVAL;
+    for (long e = 0; e < m * k; ++e)
+        if (!d_a[e]) return MPFFT_EINVAL;
+    for (long e = 0; e < k * p; ++e)
+        if (!d_b[e]) return MPFFT_EINVAL;
+    if (!ws_ok(d_ws, ws_bytes, mm_layout(P, m, k, p).bytes)) return MPFFT_ENOMEM;
+    return run_matmul(P, (int)m, (int)k, (int)p, (u64 *const *)d_r, (unsigned char *)d_ws, (hipStream_t)stream,
+                      [&](int e, const u64 **d) {
+                          *d = e < m * k ? d_a[e] : d_b[e - m * k];
+                          return (int)MPFFT_OK;
+                      });
+}
+
+// Host pointers: the context's io buffer holds one operand at a time (its copy is queued in front of
+// its forward passes, on the same stream) and, behind it, the m p results
+int mpfft_matmul_ex(uint64_t *const *r, long m, long k, long p, const uint64_t *const *a, const uint64_t *const *b, long n1,
+                    long n2, unsigned long depth, unsigned long w)
+{
+    Plan P;
+    int rc = make_plan_matmul(&P, m, k, p, n1, n2, depth, w);
+    if (rc) return rc;
+    if (!r || !a || !b) return MPFFT_EINVAL;
+    for (long e = 0; e < m * p; ++e)
+        if (!r[e]) return MPFFT_EINVAL;
+    for (long e = 0; e < m * k; ++e)
+        if (!a[e]) return MPFFT_EINVAL;
+    for (long e = 0; e < k * p; ++e)
+        if (!b[e]) return MPFFT_EINVAL;
+    const long nin = n1 > n2 ? n1 : n2;
+    HostCall H;
+    if ((rc = H.open(mm_layout(P, m, k, p).bytes, (size_t)(nin + m * p * P.total) * 8))) return rc;
+    u64 *d_in = H.C->io;
+    hipStream_t s = H.C->stream;
+    u64 *d_rs[MM_MAX * MM_MAX];
+    for (long e = 0; e < m * p; ++e) d_rs[e] = d_in + nin + e * P.total;
+    rc = run_matmul(P, (int)m, (int)k, (int)p, d_rs, H.C->ws, s, [&](int e, const u64 **d) {
+        const bool isa = e < m * k;
+        HIPCHK(hipMemcpyAsync(d_in, isa ? a[e] : b[e - m * k], (size_t)(isa ? n1 : n2) * 8, hipMemcpyHostToDevice, s));
+        *d = d_in;
+        return (int)MPFFT_OK;
+    });
+    if (rc) {
+        (void)hipStreamSynchronize(s);
+        return rc;
+    }
+    for (long e = 0; e < m * p; ++e)
+        HIPCHK(hipMemcpyAsync(r[e], d_rs[e], (size_t)P.total * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return MPFFT_OK;
+}
+
+int mpfft_matmul_auto(uint64_t *const *r, long m, long k, long p, const uint64_t *const *a, const uint64_t *const *b, long n1,
+                      long n2)
+{
+    if (m < 1 || m > MM_MAX || k < 1 || k > MM_MAX || p < 1 || p > MM_MAX) return MPFFT_EINVAL;
+    unsigned long d = 0, wv = 0;
+    const int rc = mpfft_dot_choose(k, n1, n2, &d, &wv);
+    if (rc) return rc;
+    return mpfft_matmul_ex(r, m, k, p, a, b, n1, n2, d, wv);
+}
+
+// The dot plan's seven fields with the pointwise field replaced: what writes the caches + what forms a
+// result entry's sum
+int mpfft_matmul_stage_kernels(long m, long k, long p, long n1, long n2, unsigned long depth, unsigned long w, char *buf,
+                               size_t len)
+{
+    Plan P;
+    int rc = make_plan_matmul(&P, m, k, p, n1, n2, depth, w);
+    if (rc) return rc;
+    std::string names = stage_kernel_names(P);
+    size_t f0 = 0;   // the third of the seven ';'-joined fields
+    for (int i = 0; i < 2; ++i) f0 = names.find(';', f0) + 1;
+    const size_t f1 = names.find(';', f0);
+    std::string pw = names.substr(f0, f1 - f0);
+    if (pw_family(P) == PWF_NESTED) {
+        const int lk = pwss_lk_of(P.l), M = pw_inner_limbs(P.l, lk);
+        char mm[96];
+        snprintf(mm, sizeof mm, " + k_pwmm<%d> (single launch, K=%d)", M, 1 << lk);
+        pw.replace(pw.find("k_pwss"), 6, "k_pwsx");   // the caches are written through that kernel's loaders
+        pw += mm;
+    } else {
+        pw.insert(pw.size(), " (B cached) + k_slotacc");
+    }
+    names.replace(f0, f1 - f0, pw);
+    return copy_out(names, buf, len);
+}
+
+int mpfft_matmul_stage(int stage, long m, long k, long p, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_r, long n1,
+                       long n2, unsigned long depth, unsigned long w, void *d_ws, size_t ws_bytes, void *stream, long kk,
+                       const int *ea, const int *eb)
+{
+    Plan P;
+    int rc = make_plan_matmul(&P, m, k, p, n1, n2, depth, w);
+    if (rc) return rc;
+    const bool acc = (stage & MPFFT_STAGE_ACC) != 0;
+    const int st = stage & ~MPFFT_STAGE_ACC;
+    if (st != MPFFT_STAGE_MM_STORE && st != MPFFT_STAGE_MM_POINTWISE)   // the dot workspace sits at the front
+        return mpfft_dot_stage(stage, k, d_a, d_b, d_r, n1, n2, depth, w, d_ws, ws_bytes, stream);
+    const MmLayout L = mm_layout(P, m, k, p);
+    if (!ea || (acc && st != MPFFT_STAGE_MM_POINTWISE)) return MPFFT_EINVAL;
+    if (!ws_ok(d_ws, ws_bytes, L.bytes)) return MPFFT_ENOMEM;
+    unsigned char *ws = (unsigned char *)d_ws;
+    Exec X(P, (hipStream_t)stream);
+    X.single(ws);
+    X.pre_make = true;   // (like mpfft_dot_stage it never fuses row levels)
+    if (st == MPFFT_STAGE_MM_STORE) {
+        if (ea[0] < 0 || ea[0] >= L.ncache) return MPFFT_EINVAL;
+        X.pre = ws + L.off_cache + (size_t)ea[0] * L.stride;
+        return X.precomp_store(ea[0] < m * k ? 0 : 1);
+    }
+    if (!eb || kk < 1 || kk > MM_MAX) return MPFFT_EINVAL;
+    for (long i = 0; i < kk; ++i)
+        if (ea[i] < 0 || ea[i] >= L.ncache || eb[i] < 0 || eb[i] >= L.ncache) return MPFFT_EINVAL;
+    return X.pointwise_mm(ws + L.off_cache, L.stride, (int)kk, ea, eb, acc);
 }
 
 // ---- signed sums of products (mpfft_sdot_*, MPFFT_VERSION 9; sdot.hpp) -------------------------

@@ -35,6 +35,13 @@ typedef void (*pw_mulpre_fn)(uint64_t *, uint64_t *, int *, const unsigned char 
 pw_mulpre_fn pw_get_mulpre(int M, int lk, int fuse = 0);
 size_t pw_pre_record_bytes(int M, int K);
 
+// Small matrix products (pwmm.hip): k_pwmm<M, lk, acc>(caches, stride, kk, ea, eb, l, C): C[slot] (acc: +)=
+// the sum of kk <= 4 products of k_pwsx records, record regions ea_i, eb_i (8 bits each) of `stride`
+// bytes from `caches`; k_pwss's LDS and launch shape; nullptr if not built
+typedef void (*pw_mm_fn)(const unsigned char *, unsigned long long, int, unsigned, unsigned, int, uint64_t *, uint64_t *,
+                         int *);
+pw_mm_fn pw_get_mm(int M, int lk, bool acc = false);
+
 // Inner ring for a product mod 2^(64 l) + 1 cut into K = 2^lk pieces: the smallest even M
 // (limbs) with 64 M >= 2 (64 l / K) + lk + 4: the pair-fused inputs (pieces of x0 +- x1) are
 // below 2^(B+1) (1 + 2^-64) in magnitude, so |c_t| < K 2^(2B+2) (1 + 2^-62) < 2^(N'-1)

@@ -1685,3 +1685,99 @@ __global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_wpe<
         if (threadIdx.x == 0) stamp[7] = __builtin_amdgcn_s_memtime();
     }
 }
+
+// ---------------------------------------------------------------------------
+// small matrix products (mpfft_matmul_*): every operand's slots are cached once as k_pwsx records,
+// and k_pwmm forms one result entry's slot from kk pairs of records -- the kk inner products summed
+// in the inner ring, then one inverse transform and one output stage.
+// ---------------------------------------------------------------------------
+constexpr int PW_MM_MAX = 4;   // terms of one sum (MPFFT_MM_MAX)
+
+// acc <- acc + (-1)^neg (W + Tw 2^N'), acc = A + Ta 2^N': one 32-bit carry chain; a subtraction
+// adds ~W + 1 = 2^N' - W, so its carry out counts one less
+template <int M>
+__host__ __device__ __forceinline__ void pw_mm_add(u64 (&A)[M], int &Ta, const u64 (&W)[M], int Tw, bool neg)
+{
+    const u32 m = neg ? ~0u : 0u;
+    u32 c = neg ? 1u : 0u;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const u32 lo = __builtin_addc((u32)A[j], (u32)W[j] ^ m, c, &c);
+        const u32 hi = __builtin_addc((u32)(A[j] >> 32), (u32)(W[j] >> 32) ^ m, c, &c);
+        A[j] = ((u64)hi << 32) | lo;
+    }
+    Ta += (int)c + (neg ? -1 - Tw : Tw);
+}
+
+// waves per SIMD k_pwmm is compiled for: two records, the product and the accumulator are live
+// across pw_mulmod (k_pwsp: one record less), which does not fit k_pwss's 128 VGPRs where the
+// product's own LDS column (the Karatsuba park, the tight form's product words) leaves no room
+// for the accumulator
+template <int M, int LK>
+__host__ __device__ constexpr int pw_mm_wpe()
+{
+    // M = 10 fits k_pwss's budget (96 VGPRs); M = 18: 155 VGPRs, three workgroups per CU; M = 20:
+    // 162 VGPRs, one workgroup of eight waves per CU.  At k_pwss's 128 VGPRs the two larger sizes
+    // spilled 156 and 124 bytes per lane
+    return M == 10 ? pw_wpe<M, LK>() : M == 18 ? 3 : 2;
+}
+
+// k_pwmm<M, LK, ACC>: C[slot] <- (ACC: C[slot] +) sum_{i < kk} rec(ea_i)[slot] * rec(eb_i)[slot] mod 2^N + 1,
+// one workgroup of K threads per slot.  caches: cache regions of `stride` bytes each, region e
+// holding the k_pwsx records of one operand (pw_pre_slot_bytes per slot); ea, eb: the kk <= PW_MM_MAX
+// region indices of the terms' factors, 8 bits each, term 0 lowest.  The records are only read.
+// The pending exponent of a record is a function of the thread index alone (pw_transform: the
+// weight and the twiddles of the levels whose bit t has; pw_canon leaves it), so every term's
+// product carries the same 2^(Pa + Pb) and the sum needs no rotation: products are added with
+// their signs Sa ^ Sb.  After kk signed additions of products with tops in {-1, 0} the
+// accumulator's top lies in [-2 kk, 2 kk]; pw_norm's device form and pw_combine's T_q != -1
+// branch take any such small top.
+template <int M, int LK, bool ACC>
+__global__ __launch_bounds__(1 << LK) __attribute__((amdgpu_waves_per_eu(pw_mm_wpe<M, LK>()))) void k_pwmm(const unsigned char *caches, unsigned long long stride, int kk, unsigned ea,
+                                                  unsigned eb, int l, u64 *digC, u64 *cbC, int *topC)
+{
+    // a record's pieces are below 2^(B + 2) in magnitude behind the quad loaders (pdispatch.hpp: 2 B + lk + 6
+    // for one product); PW_MM_MAX summed products take ceil(log2 PW_MM_MAX) = 2 bits more
+    static_assert(PW_MM_MAX <= 4 && 64 * M >= 2 * 64 * pw_piece_limbs<M, LK>() + LK + 6 + 2,
+                  "inner headroom for PW_MM_MAX summed products");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int K = 1 << LK;
+    constexpr unsigned N2 = 128 * M;
+    const int t = threadIdx.x;
+    const auto [X, Xw, TT, H] = pw_lds_carve<M, LK>(smem);
+    const int cbw = cb_words(l);
+    const long slot = blockIdx.x;
+    u64 Z[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) Z[j] = 0;
+    int Tz = 0;
+    unsigned Pz = 0;
+#pragma unroll 1
+    for (int i = 0; i < kk; ++i) {
+        const unsigned char *ra = caches + (size_t)((ea >> (8 * i)) & 255u) * stride;
+        const unsigned char *rb = caches + (size_t)((eb >> (8 * i)) & 255u) * stride;
+        u64 La[M], Lb[M], W[M];
+        const u32 ma = pw_pre_load<M, LK>(La, ra, slot, pw_launder(t));
+        const u32 mb = pw_pre_load<M, LK>(Lb, rb, slot, pw_launder(t));
+        int ca, cb, Sa, Sb, Tw;
+        unsigned Pa, Pb;
+        pw_pre_unpack(ma, ca, Sa, Pa);
+        pw_pre_unpack(mb, cb, Sb, Pb);
+        // the product's sign and exponent cross the digit products as one opaque word (k_pwsp)
+        const int meta = pw_launder((int)pw_pre_pack(0, Sa ^ Sb, pw_mod(Pa + Pb, N2)));
+        if constexpr (pw_kara<M>()) {
+            pw_mulmod<M>(W, Tw, La, ca, Lb, cb, PwParkLds{Xw + t, K});
+        } else if (pw_tight(K)) {
+            pw_mulmod<M>(PwLdsZ{Xw + t, K}, Tw, La, ca, Lb, cb);
+#pragma unroll
+            for (int j = 0; j < M; ++j) W[j] = ((u64)Xw[(2 * j + 1) * K + t] << 32) | Xw[2 * j * K + t];
+        } else {
+            pw_mulmod<M>(W, Tw, La, ca, Lb, cb);
+        }
+        int cz, Sz;
+        pw_pre_unpack((u32)meta, cz, Sz, Pz);
+        pw_mm_add<M>(Z, Tz, W, Tw, Sz != 0);
+    }
+    pw_slot_tail<M, LK>(Z, Tz, 0, Pz, X, Xw, TT, t, nullptr);
+    pw_slot_output<M, LK, K, ACC>(X, TT, H, digC + (size_t)slot * l, cbC + (size_t)slot * cbw, topC + slot, l, t);
+}

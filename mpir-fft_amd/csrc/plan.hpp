@@ -451,6 +451,35 @@ static int make_plan_pre(Plan *p, long n1, long n2, unsigned long depth, unsigne
     return MPFFT_OK;
 }
 
+// Small matrix product (mpfft_matmul_*): R = X Y, X m x k, Y k x p, on the dot plan at K = k.  The dot
+// workspace at the front -- A's and B's arrays are the staging arrays of an X and a Y operand's
+// forward transform, C holds one result entry's pointwise sum -- and behind it one cache region per
+// matrix entry (plan_pre_bytes, the layout mpfft_precomp_* writes), X's entries row-major, then Y's,
+// at a uniform 256-byte aligned stride.  A dot workspace laid at the front is valid as it stands.
+static const int MM_MAX = 4;
+struct MmLayout {
+    size_t off_cache, stride, bytes;
+    int ncache;
+};
+static MmLayout mm_layout(const Plan &P, long m, long k, long p)
+{
+    MmLayout L;
+    L.ncache = (int)(m * k + k * p);
+    L.stride = align_up(plan_pre_bytes(P), 256);
+    L.off_cache = align_up(P.bytes, 256);
+    L.bytes = L.off_cache + (size_t)L.ncache * L.stride;
+    return L;
+}
+// the dot plan at K = k; MPFFT_EINVAL for m, k or p outside [1, MM_MAX]
+static int make_plan_matmul(Plan *p, long m, long k, long pp, long n1, long n2, unsigned long depth, unsigned long w)
+{
+    if (m < 1 || m > MM_MAX || k < 1 || k > MM_MAX || pp < 1 || pp > MM_MAX) {
+        memset(p, 0, sizeof(*p));
+        return MPFFT_EINVAL;
+    }
+    return make_plan_dot(p, k, n1, n2, depth, w);
+}
+
 // Negacyclic plan (nega.hpp): a b mod 2^B + 1, B = 64 L, as the length-2n negacyclic convolution
 // of bits1 = B / 2n bit pieces.  The multiply's kernel families and its split for an
 // untruncated transform of these (depth, w) (make_plan's choice at Tr = NR); nothing is
